@@ -8,10 +8,22 @@ HBM replay ring of N * K rows -- the fused play_one_step + deque.append of src/d
 with the boards resident in VGPRs.  value = env steps/s over all ranks = N * K * world * steps /
 (max over ranks of the timed wall time).
 
-Extra fields: the one-launch-per-step kernel (g2048_env_step, hipGraph-replayed) at the same N,
-DQN updates/s + full training-loop iterations at B = 8192 for the dense-64 / conv / dense-ref
-nets in fp32 (fused HIP kernels where they exist) and fp64 (the reference's precision), the CPU
-baselines (oracle env on every host core; the reference train_step in fp64 on torch CPU).
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what that figure needs: set up,
+warm up, time the N launches, write the outputs if `--dump-outputs DIR` is given, print the line.
+
+`--full` adds every other leg to the line: the same launch at further K, into an HBM-streamed
+ring and at large N, the one-launch-per-step kernel (g2048_env_step, hipGraph-replayed) at the
+same N, DQN updates/s + full training-loop iterations at B = 8192 for the dense-64 / conv /
+dense-ref nets in fp32 (fused HIP kernels where they exist) and fp64 (the reference's precision),
+the CPU baselines (oracle env on every host core; the reference train_step in fp64 on torch CPU).
+The options that shape those legs are refused without `--full`.
+
+`--dump-outputs DIR` writes what the last timed launch left a caller -- the boards, scores,
+episode counters and step clocks, and the launch's replay rows -- as DIR/<name>.npy (float32 for
+the byte arrays, float64 for the integer ones; a fixed seeded sample of rows where an array is
+large).  The env state is then put back after the time-based clock settle to what it was after
+the warm-up, so the timed launches start from the same boards in every run with the same
+arguments and two builds can be compared array for array.
 
 Multi-GPU: one process per GPU (`--gpus N` starts them through torch.distributed.run when no
 torchrun environment is present), boards sharded by board_offset = rank * N, no collective on
@@ -138,11 +150,23 @@ def learner_roofline(net: str, dtype: str, batch: int, update_s: float, params: 
     return out
 
 
-def parse():
+# the options of the legs beside the headline: they need --full
+FULL_ONLY = ("rollout_k_extra", "large_n", "hbm_ring_launches", "step_steps", "train",
+             "train_dtypes", "train_updates", "batch", "replay", "no_cpu_baseline", "cpu_seconds")
+
+
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200, help="timed rollout launches")
     p.add_argument("--warmup", type=int, default=20, help="untimed rollout launches")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline (further K, HBM ring, large N, "
+                        "one launch per step, the learners, the CPU baselines); the options "
+                        "below that shape those legs need it")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed launch computed (env state + a seeded sample "
+                        "of its replay rows) as DIR/<name>.npy")
     p.add_argument("--boards", type=int, default=65536)
     p.add_argument("--rollout-k", type=int, default=64, help="env steps per rollout launch")
     p.add_argument("--rollout-k-extra", default="256",
@@ -169,7 +193,15 @@ def parse():
     p.add_argument("--replay", type=int, default=1 << 20)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=8.0)
-    return p.parse_args()
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        given = [o for o in FULL_ONLY if getattr(args, o) != p.get_default(o)]
+        if given:
+            p.error("the legs beside the headline run only with --full: "
+                    + ", ".join("--" + o.replace("_", "-") for o in given))
+    return args
 
 
 # RCCL ("nccl") in production; G2048_BENCH_BACKEND=gloo rehearses several ranks on one GPU
@@ -348,8 +380,59 @@ def capture(fn, n_steps: int):
     return g
 
 
+# ------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_ROWS = 1 << 17  # rows kept of each array: every file together stays under 64 MB
+DUMP_SEED = 0x2048
+
+
+def sample_rows(n_rows: int, max_rows: int = DUMP_MAX_ROWS, seed: int = DUMP_SEED):
+    """The rows of an n_rows array that --dump-outputs keeps: None (all of them) up to max_rows,
+    else max_rows indices drawn with numpy's frozen legacy generator from a fixed seed, sorted --
+    the same rows in every run and every build."""
+    import numpy as np
+
+    if n_rows <= max_rows:
+        return None
+    return np.sort(np.random.RandomState(seed).randint(0, n_rows, size=max_rows))
+
+
+def dump_outputs(out_dir: str, env, rb) -> dict:
+    """What the last rollout launch left its caller, as out_dir/<name>.npy: the env state (board,
+    score_start = meta, episodes = ep, clock) and the ring's transitions (replay_s / _s2 / _a /
+    _r / _d with the ring rows kept in replay_rows, and replay_count).  Byte arrays go out as
+    float32, int32 / int64 ones as float64 (exact).  Returns {name: shape}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    written = {}
+
+    def put(name, t, rows):
+        if rows is not None:
+            t = t[torch.as_tensor(rows, device=t.device)]
+        a = t.cpu().numpy().astype(np.float32 if t.dtype == torch.uint8 else np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+
+    boards = sample_rows(env.n)
+    put("board", env.board, boards)
+    put("score_start", env.meta.t(), boards)  # [N, 2]: score, clock at which the episode began
+    put("episodes", env.ep, boards)
+    put("clock", env.clock, sample_rows(env.clock.numel()))
+    if boards is not None:
+        np.save(os.path.join(out_dir, "board_rows.npy"), boards.astype(np.float64))
+    rows = sample_rows(rb.capacity)
+    for name in ("s", "s2", "a", "r", "d"):
+        put("replay_" + name, getattr(rb, name), rows)
+    put("replay_count", rb.count, None)
+    if rows is not None:
+        np.save(os.path.join(out_dir, "replay_rows.npy"), rows.astype(np.float64))
+    return written
+
+
 # ------------------------------------------------------------------ headline: the rollout kernel
-def bench_rollout(args, world, rank, dev, k_override=None, n_override=None, ring_launches=1):
+def bench_rollout(args, world, rank, dev, k_override=None, n_override=None, ring_launches=1,
+                  dump_dir=None):
     """W untimed + `steps` timed k_rollout launches (K env steps of every board each, replay
     append into an N*K*ring_launches-row ring), replayed from hipGraphs of --graph-steps launches
     (the kernel reads its step clock and ring row from device memory, so a replay is a fresh
@@ -375,7 +458,15 @@ def bench_rollout(args, world, rank, dev, k_override=None, n_override=None, ring
         g.replay()
     for _ in range(max(args.warmup, 1)):
         launch()
+    # the settle runs for a time, not a count: with --dump-outputs the env state is put back
+    # after it, so the timed launches start from the same boards in every run (a launch
+    # rewrites the whole ring, so the ring needs no restoring)
+    state = (env.board, env.meta, env.ep, env.clock, rb.count)
+    saved = [t.clone() for t in state] if dump_dir else None
     settle_ms = settle(graphs[0][0].replay, args.settle_ms)
+    if saved:
+        for t, s in zip(state, saved):
+            t.copy_(s)
 
     def run_all():
         for g, reps in graphs:
@@ -385,10 +476,11 @@ def bench_rollout(args, world, rank, dev, k_override=None, n_override=None, ring
     wall, ev = timed(world, dev, run_all, 1)
     env.check_errors()
     assert int(rb.count) == n * k * ring_launches
+    dumped = dump_outputs(dump_dir, env, rb) if dump_dir and rank == 0 else None  # its own shard
     # the bytes a launch's lines see between two uses: the ring (rows of R launches) + env state
     ws = ROLLOUT_BYTES * n * k * ring_launches + n * (16 + 8 + 16) + 8 * ((n + 63) // 64)
     return dict(wall=wall, ev_s=ev, n=n, k=k, settle_ms=settle_ms, board_offset=rank * n,
-                working_set=ws)
+                working_set=ws, dumped=dumped)
 
 
 def rollout_roofline(r, steps, rec):
@@ -565,7 +657,7 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     world, rank, dev = setup_dist(args)
-    ro = bench_rollout(args, world, rank, dev)
+    ro = bench_rollout(args, world, rank, dev, dump_dir=args.dump_outputs)
     n, k = ro["n"], ro["k"]
     value = n * k * world * args.steps / ro["wall"]
     ranges = [[ro["board_offset"], n]]
@@ -573,6 +665,48 @@ def main():
         got = [None] * world
         dist.all_gather_object(got, ranges[0])
         ranges = got
+    extra = full_legs(args, world, rank, dev, n, k) if args.full else {}
+    roof = rollout_roofline(ro, args.steps, pmc_record(f"k_rollout@{n}x{k}"))
+    roof["kernel"] = ("k_rollout_lean (g2048_env_rollout: ring in one buffer window, auto-reset, "
+                      "no episode log)")
+    if rank == 0:
+        line = {
+            "metric": METRIC,
+            "value": value,
+            "unit": "env steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ro["wall"] / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic (fresh boards from Philox spawns, uniform random actions)",
+            "config": {"workload": "BASELINE configs[1]: 64k vectorised boards per GPU, env step "
+                                   "only (no learner), random policy; one step = one rollout "
+                                   f"launch moving every board {k} times with replay append",
+                       "boards_per_gpu": n, "global_boards": n * world,
+                       "env_steps_per_launch": n * k, "replay_rows": n * k,
+                       "rank_boards": ranges,
+                       "parallelism": f"dp{world} (boards sharded, no collective)"},
+            "roofline": roof,
+            "full": args.full,
+            "cpu_baseline": extra.pop("cpu_baseline", None),
+            "dist": {"process_group": distributed(),
+                     "backend": dist.get_backend() if distributed() else None,
+                     "capture_error_mode": _capture_mode_name()},
+        }
+        if ro["dumped"]:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": ro["dumped"]}
+        line.update(extra)
+        print(json.dumps(line), flush=True)
+    if distributed():
+        dist.destroy_process_group()
+
+
+def full_legs(args, world, rank, dev, n, k) -> dict:
+    """--full: every leg beside the headline, as the fields they add to the line."""
     # the same launch at further K: a launch's first steps run slower than its steady state
     # (DESIGN.md 4.2), so the per-step time falls with K
     ksweep = []
@@ -639,49 +773,18 @@ def main():
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baselines(args)
-    roof = rollout_roofline(ro, args.steps, pmc_record(f"k_rollout@{n}x{k}"))
-    roof["kernel"] = ("k_rollout_lean (g2048_env_rollout: ring in one buffer window, auto-reset, "
-                      "no episode log)")
-    if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": value,
-            "unit": "env steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ro["wall"] / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (fresh boards from Philox spawns, uniform random actions)",
-            "config": {"workload": "BASELINE configs[1]: 64k vectorised boards per GPU, env step "
-                                   "only (no learner), random policy; one step = one rollout "
-                                   f"launch moving every board {k} times with replay append",
-                       "boards_per_gpu": n, "global_boards": n * world,
-                       "env_steps_per_launch": n * k, "replay_rows": n * k,
-                       "rank_boards": ranges,
-                       "parallelism": f"dp{world} (boards sharded, no collective)"},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "dist": {"process_group": distributed(),
-                     "backend": dist.get_backend() if distributed() else None,
-                     "capture_error_mode": _capture_mode_name()},
-        }
-        if hbm64:
-            line["rollout_64k_hbm"] = hbm64
-        if ksweep:
-            line["rollout_k_sweep"] = ksweep
-        if large:
-            line["rollout_large_n"] = large
-        if step:
-            line["step_kernel"] = step
-        if train:
-            line["learner"] = train
-        print(json.dumps(line), flush=True)
-    if distributed():
-        dist.destroy_process_group()
+    out = {"cpu_baseline": cpu}
+    if hbm64:
+        out["rollout_64k_hbm"] = hbm64
+    if ksweep:
+        out["rollout_k_sweep"] = ksweep
+    if large:
+        out["rollout_large_n"] = large
+    if step:
+        out["step_kernel"] = step
+    if train:
+        out["learner"] = train
+    return out
 
 
 def _capture_mode_name() -> str:

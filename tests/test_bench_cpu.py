@@ -52,6 +52,34 @@ def test_rollout_roofline_residency():
     assert t["traffic"] == 2.0e8 and "profiles/r04/pmc.json" in t["traffic_source"]
 
 
+def test_plain_run_refuses_the_other_legs_options(capsys):
+    """A plain run times the headline only: --full is off by default, and an option that shapes
+    one of the other legs is refused without it instead of being ignored."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.steps == 7 and a.warmup == 2 and a.dump_outputs is None
+    assert bench.parse(["--full", "--train", "conv", "--no-cpu-baseline"]).full is True
+    assert bench.parse(["--dump-outputs", "out", "--boards", "1024"]).dump_outputs == "out"
+    for opts in (["--train", "conv"], ["--no-cpu-baseline"], ["--step-steps", "0"],
+                 ["--large-n", ""], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse(opts)
+    assert "--full" in capsys.readouterr().err
+
+
+def test_dump_sample_rows_fixed():
+    """--dump-outputs keeps every row of a small array and the same sorted sample of a large one
+    in every run; the files of the default run stay under 64 MB together."""
+    assert bench.sample_rows(bench.DUMP_MAX_ROWS) is None
+    r = bench.sample_rows(65536 * 64)
+    assert r.shape == (bench.DUMP_MAX_ROWS,) and (r[1:] >= r[:-1]).all()
+    assert 0 <= r[0] and r[-1] < 65536 * 64
+    assert (r == bench.sample_rows(65536 * 64)).all()
+    m = bench.DUMP_MAX_ROWS
+    # largest case: m boards and m ring rows kept; u8 -> 4 B, i32 / i64 -> 8 B per element
+    worst = m * (16 * 4 + 2 * 8 + 4 * 8 + 8 + 8) + m * (2 * 16 * 4 + 4 + 8 + 4 + 8) + 8
+    assert worst < 64e6
+
+
 def test_pmc_summary_steps_per_launch():
     """Issue counters are normalised per env step: K of the rollout key, with or without the
     ring-launches suffix (round 4 parsed every key as K = 1)."""

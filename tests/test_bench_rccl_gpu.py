@@ -21,8 +21,8 @@ def test_bench_rccl_world1():
     env = dict(os.environ, G2048_BENCH_DIST="1", PYTHONUNBUFFERED="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
-           "--step-steps", "200", "--rollout-k-extra", "", "--large-n", "",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20",
+           "--warmup", "5", "--step-steps", "200", "--rollout-k-extra", "", "--large-n", "",
            "--hbm-ring-launches", "0", "--train", "conv,dense64,dense@512",
            "--train-dtypes", "fp32,fp64", "--train-updates", "20", "--no-cpu-baseline"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)

@@ -134,8 +134,8 @@ def test_bench_two_ranks():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, G2048_BENCH_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
-                          "--steps", "20", "--warmup", "5", "--step-steps", "200",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full",
+                          "--gpus", "2", "--steps", "20", "--warmup", "5", "--step-steps", "200",
                           "--train", "dense64,dense@512", "--train-dtypes", "fp32,fp64",
                           "--train-updates", "20", "--large-n", "524288x16",
                           "--no-cpu-baseline"], capture_output=True, text=True, env=env,

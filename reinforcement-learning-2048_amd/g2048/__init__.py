@@ -5,7 +5,11 @@ src/dqn_lib.py): the env step, replay buffer and train_step, batched over tens o
 boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI include/g2048.h).
 """
 from ._native import NativeError, load as load_native  # noqa: F401
+from . import search  # noqa: F401
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
+from .search import (SearchWeights, expectimax,  # noqa: F401
+                     generate_replay_buffer_using_expectimax)
 
 __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIONS", "NativeError",
-           "load_native"]
+           "load_native", "search", "SearchWeights", "expectimax",
+           "generate_replay_buffer_using_expectimax"]

@@ -11,6 +11,10 @@ Policies (one game per board, every board plays to its end):
            When every legal Q is negative the argmax lands on an illegal move; the board then no
            longer changes and the reference loops forever.  Here such a game stops at once and is
            flagged `stuck` (rule="legal" restricts the argmax to legal moves instead).
+  expectimax  the searching player the reference leaves empty (play_state_space_search_game,
+           :87-88): depth-limited expectimax on the GPU (g2048.search, search_depth player moves
+           deep, search_weights), then the env step with the chosen moves.  Always a legal move,
+           so no game gets stuck; history tuples as play_game's.
 
 Results follow the reference's bookkeeping: `moves` = steps taken (history length, terminal
 step included), `merge_score`, `max_tile`; `max_tile_frequency()` is notebook_utils'
@@ -22,7 +26,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import qnet
+from . import qnet, search
 from .env import VecEnv2048
 from .nets import Conv2048
 
@@ -104,6 +108,9 @@ class GameResults:
         self.moves = moves                # int64 [n] steps taken (history length)
         self.stuck = stuck                # bool  [n] greedy game stopped on an illegal argmax
         self.histories = histories        # list of per-game histories (first record_games)
+        # per step, for the first record_games games, whether finished or not: device tensors
+        # (board before, action, reward, merge score before, board after); set by play()
+        self.trace = []
 
     def __len__(self):
         return len(self.max_tile)
@@ -124,7 +131,8 @@ class BatchedPlayer:
 
     def __init__(self, n_games: int, device="cuda:0", seed: int = 0, model=None,
                  encoding: str = "normalized", rule: str = "reference", p4: float = 0.5,
-                 record_games: int = 0, max_moves: int = 1 << 20, check_every: int = 32):
+                 record_games: int = 0, max_moves: int = 1 << 20, check_every: int = 32,
+                 search_depth: int = 2, search_weights=None):
         self.n = int(n_games)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -135,6 +143,9 @@ class BatchedPlayer:
         self.record = int(min(record_games, self.n))
         self.max_moves = int(max_moves)
         self.check_every = int(check_every)
+        if not 1 <= int(search_depth) <= search.MAX_DEPTH:
+            raise ValueError(f"search_depth must be in [1, {search.MAX_DEPTH}]")
+        self.search_depth, self.search_weights = int(search_depth), search_weights
 
     def _env(self, egreedy="compat"):
         return VecEnv2048(self.n, seed=self.seed, device=self.device, p4=self.p4,
@@ -155,8 +166,8 @@ class BatchedPlayer:
     def play(self, policy: str = "random") -> GameResults:
         if policy == "greedy" and self.model is None:
             raise ValueError("the greedy policy needs a model")
-        if policy not in ("random", "upleft", "greedy"):
-            raise ValueError("policy must be 'random', 'upleft' or 'greedy'")
+        if policy not in ("random", "upleft", "greedy", "expectimax"):
+            raise ValueError("policy must be 'random', 'upleft', 'greedy' or 'expectimax'")
         env = self._env(egreedy="fixed" if policy == "random" else "compat")
         dev = self.device
         n = self.n
@@ -182,6 +193,12 @@ class BatchedPlayer:
                 reward, _, legal = env.step(act)
                 moved = ((legal.to(torch.int64) >> act) & 1).bool()
                 ended = ul.update(moved)
+                newly_stuck = None
+            elif policy == "expectimax":
+                act, _ = search.expectimax(env.board, self.search_depth, self.search_weights,
+                                           self.p4, values=False)
+                reward, done, _ = env.step(act)
+                ended = done.bool()
                 newly_stuck = None
             else:
                 legal = env.legal_mask()
@@ -210,8 +227,10 @@ class BatchedPlayer:
         env.check_errors()
         max_tile = torch.where(f_max > 0, torch.ones_like(f_max) << f_max, f_max)
         hist = self._histories(policy, rec, f_moves[:k].cpu().numpy()) if k else []
-        return GameResults(policy, max_tile.cpu().numpy(), f_score.cpu().numpy(),
-                           f_moves.cpu().numpy(), stuck.cpu().numpy(), hist)
+        res = GameResults(policy, max_tile.cpu().numpy(), f_score.cpu().numpy(),
+                          f_moves.cpu().numpy(), stuck.cpu().numpy(), hist)
+        res.trace = rec
+        return res
 
     @staticmethod
     def _histories(policy, rec, moves):

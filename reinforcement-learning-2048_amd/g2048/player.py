@@ -15,6 +15,9 @@ Policies (one game per board, every board plays to its end):
            :87-88): depth-limited expectimax on the GPU (g2048.search, search_depth player moves
            deep, search_weights), then the env step with the chosen moves.  Always a legal move,
            so no game gets stuck; history tuples as play_game's.
+  ntuple   the greedy afterstate policy of an n-tuple value network (g2048.ntuple, ntuple=net):
+           argmax over the legal moves of gain + V(afterstate), then the env step.  Always a legal
+           move, so no game gets stuck; history tuples as play_game's.
 
 Results follow the reference's bookkeeping: `moves` = steps taken (history length, terminal
 step included), `merge_score`, `max_tile`; `max_tile_frequency()` is notebook_utils'
@@ -132,7 +135,7 @@ class BatchedPlayer:
     def __init__(self, n_games: int, device="cuda:0", seed: int = 0, model=None,
                  encoding: str = "normalized", rule: str = "reference", p4: float = 0.5,
                  record_games: int = 0, max_moves: int = 1 << 20, check_every: int = 32,
-                 search_depth: int = 2, search_weights=None):
+                 search_depth: int = 2, search_weights=None, ntuple=None):
         self.n = int(n_games)
         self.device = torch.device(device)
         self.seed = int(seed)
@@ -146,6 +149,7 @@ class BatchedPlayer:
         if not 1 <= int(search_depth) <= search.MAX_DEPTH:
             raise ValueError(f"search_depth must be in [1, {search.MAX_DEPTH}]")
         self.search_depth, self.search_weights = int(search_depth), search_weights
+        self.ntuple = ntuple
 
     def _env(self, egreedy="compat"):
         return VecEnv2048(self.n, seed=self.seed, device=self.device, p4=self.p4,
@@ -166,8 +170,11 @@ class BatchedPlayer:
     def play(self, policy: str = "random") -> GameResults:
         if policy == "greedy" and self.model is None:
             raise ValueError("the greedy policy needs a model")
-        if policy not in ("random", "upleft", "greedy", "expectimax"):
-            raise ValueError("policy must be 'random', 'upleft', 'greedy' or 'expectimax'")
+        if policy == "ntuple" and self.ntuple is None:
+            raise ValueError("the ntuple policy needs a network (ntuple=NTupleNetwork)")
+        if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple"):
+            raise ValueError("policy must be 'random', 'upleft', 'greedy', 'expectimax' or "
+                             "'ntuple'")
         env = self._env(egreedy="fixed" if policy == "random" else "compat")
         dev = self.device
         n = self.n
@@ -197,6 +204,11 @@ class BatchedPlayer:
             elif policy == "expectimax":
                 act, _ = search.expectimax(env.board, self.search_depth, self.search_weights,
                                            self.p4, values=False)
+                reward, done, _ = env.step(act)
+                ended = done.bool()
+                newly_stuck = None
+            elif policy == "ntuple":
+                act, _, _ = self.ntuple.act(env.board, q=False)
                 reward, done, _ = env.step(act)
                 ended = done.bool()
                 newly_stuck = None

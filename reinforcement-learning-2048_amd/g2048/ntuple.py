@@ -11,6 +11,8 @@ tests/ntuple_ref.py.
   NTupleNetwork     owns the int32 table on the device: values(), act(), save() / load()
   NTupleTrainer     self-play: k x (td_step, env.step) with no host sync, episodes from the log
   BatchedPlayer(..., ntuple=net).play("ntuple")   whole games under the greedy afterstate policy
+  NTupleNetwork.search / play("ntuple_search")    expectimax with the table at the leaves
+                                                  (g2048.ntsearch, a library of its own)
 
 The binding is this module's own (not in _native.SIGNATURES: libg2048.so's ABI stays as it is).
 There is no CPU fallback: a missing library or a non-GPU tensor raises.
@@ -200,6 +202,15 @@ class NTupleNetwork:
                                           N.ptr(qs), N.ptr(acts), N.ptr(aft), dev.index,
                                           N.stream_of(dev)), "g2048_ntuple_act")
         return acts, qs, aft
+
+    def search(self, boards: torch.Tensor, depth: int = 2, p4: float = 0.5, values=True,
+               actions=True, values_out=None, actions_out=None):
+        """Expectimax `depth` player moves deep with this table at the leaves
+        (g2048.ntsearch.expectimax): (actions u8 [n], values i64 [n, 4]).  Depth 1 is act()."""
+        from . import ntsearch
+
+        return ntsearch.expectimax(self, boards, depth, p4, values, actions, values_out,
+                                   actions_out)
 
     def td_step(self, boards, prev, has_prev, lr_num, lr_shift, actions_out, delta_out,
                 err_out=None):

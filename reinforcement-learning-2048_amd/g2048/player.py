@@ -18,6 +18,10 @@ Policies (one game per board, every board plays to its end):
   ntuple   the greedy afterstate policy of an n-tuple value network (g2048.ntuple, ntuple=net):
            argmax over the legal moves of gain + V(afterstate), then the env step.  Always a legal
            move, so no game gets stuck; history tuples as play_game's.
+  ntuple_search  expectimax with the network's values at the leaves (g2048.ntsearch, ntuple=net,
+           search_depth 1..3 player moves deep, the player's p4 at the chance nodes), then the env
+           step.  Depth 1 is the ntuple policy.  Always a legal move; history tuples as
+           play_game's.
 
 Results follow the reference's bookkeeping: `moves` = steps taken (history length, terminal
 step included), `merge_score`, `max_tile`; `max_tile_frequency()` is notebook_utils'
@@ -29,7 +33,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import qnet, search
+from . import ntsearch, qnet, search
 from .env import VecEnv2048
 from .nets import Conv2048
 
@@ -172,9 +176,16 @@ class BatchedPlayer:
             raise ValueError("the greedy policy needs a model")
         if policy == "ntuple" and self.ntuple is None:
             raise ValueError("the ntuple policy needs a network (ntuple=NTupleNetwork)")
-        if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple"):
-            raise ValueError("policy must be 'random', 'upleft', 'greedy', 'expectimax' or "
-                             "'ntuple'")
+        if policy == "ntuple_search":
+            if self.ntuple is None:
+                raise ValueError("the ntuple_search policy needs a network "
+                                 "(ntuple=NTupleNetwork)")
+            if self.search_depth > ntsearch.MAX_DEPTH:
+                raise ValueError(f"the ntuple_search policy searches 1..{ntsearch.MAX_DEPTH} "
+                                 f"moves deep (search_depth = {self.search_depth})")
+        if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple", "ntuple_search"):
+            raise ValueError("policy must be 'random', 'upleft', 'greedy', 'expectimax', "
+                             "'ntuple' or 'ntuple_search'")
         env = self._env(egreedy="fixed" if policy == "random" else "compat")
         dev = self.device
         n = self.n
@@ -209,6 +220,12 @@ class BatchedPlayer:
                 newly_stuck = None
             elif policy == "ntuple":
                 act, _, _ = self.ntuple.act(env.board, q=False)
+                reward, done, _ = env.step(act)
+                ended = done.bool()
+                newly_stuck = None
+            elif policy == "ntuple_search":
+                act, _ = ntsearch.expectimax(self.ntuple, env.board, self.search_depth, self.p4,
+                                             values=False)
                 reward, done, _ = env.step(act)
                 ended = done.bool()
                 newly_stuck = None

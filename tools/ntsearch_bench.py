@@ -1,0 +1,153 @@
+"""Launch time of the expectimax over the n-tuple network (g2048.ntsearch.expectimax) by HIP
+events.
+
+For each named tuple set (TUPLES_2x4 in a 512 KiB table, TUPLES_4x6 in a 256 MiB table) the table
+is filled with random int32 and, for each batch size, fresh boards are played forward `--play`
+random steps (auto-reset on).  `NTupleNetwork.act` on those boards (the yardstick of depth 1) and
+the search at each depth are warmed up, then timed `--reps` times with an event pair each; the
+table gives the median and the spread, boards/s, leaves/s and gathers/s (a leaf is one afterstate
+whose V is read: 8 T gathers).  The leaves per board are counted on the CPU over a sample of the
+timed boards by walking the same tree (tests/expectimax_ref.py's slide), not measured.
+
+    python tools/ntsearch_bench.py [--sets 2x4 4x6] [--sizes 1024 65536] [--depths 1 2 3]
+                                   [--lib OTHER_BUILD.so] [--out FILE.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "reinforcement-learning-2048_amd"), os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def leaf_counter():
+    """root(board, depth): the afterstates whose V the search of `board` reads (with
+    repetitions, as the kernel walks them).  The count under an afterstate is a pure function of
+    (afterstate, remaining depth), so it is memoised."""
+    import expectimax_ref as R
+
+    memo = {}
+
+    def afters(key):
+        return [after for after in (bytes(R.move(key, a)[0]) for a in range(4)) if after != key]
+
+    def under(after, d):
+        if d == 0:
+            return 1
+        got = memo.get((after, d))
+        if got is None:
+            got = sum(under(nxt, d - 1)
+                      for c in range(16) if after[c] == 0 for e in (1, 2)
+                      for nxt in afters(after[:c] + bytes([e]) + after[c + 1:]))
+            memo[(after, d)] = got
+        return got
+
+    def root(board, depth):
+        return sum(under(after, depth - 1) for after in afters(bytes(int(x) for x in board)))
+
+    return root
+
+
+def timed(fn, warmup, reps):
+    import torch
+
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", nargs="+", default=["2x4", "4x6"], choices=["2x4", "4x6"])
+    ap.add_argument("--sizes", type=int, nargs="+", default=[1024, 65536])
+    ap.add_argument("--depths", type=int, nargs="+", default=[1, 2, 3])
+    ap.add_argument("--play", type=int, default=150, help="random-policy steps before timing")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--sample", type=int, default=48, help="boards walked for the leaf count")
+    ap.add_argument("--p4", type=float, default=0.5)
+    ap.add_argument("--seed", type=int, default=0x2048)
+    ap.add_argument("--lib", default=None,
+                    help="time another build of libg2048_ntsearch.so (such as one compiled with "
+                         "-DG2048_NTSEARCH_LEAF_TUPLES=4)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+
+    import g2048
+    from g2048 import ntsearch, ntuple
+
+    if not torch.cuda.is_available():
+        raise SystemExit("ntsearch_bench needs a GPU: timings come from HIP events")
+    if args.lib:
+        ntsearch.LIB_PATH = os.path.abspath(args.lib)
+    ntsearch.load()
+    dev = torch.device("cuda:0")
+    count_leaves = leaf_counter()
+    rows = []
+    for name in args.sets:
+        tuples = ntuple.TUPLES_2x4 if name == "2x4" else ntuple.TUPLES_4x6
+        T = len(tuples)
+        net = ntuple.NTupleNetwork(tuples, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(args.seed)
+        net.lut.copy_(torch.randint(-(1 << 20), 1 << 20, net.lut.shape, generator=gen, device=dev,
+                                    dtype=torch.int32))
+        for n in args.sizes:
+            env = g2048.VecEnv2048(n, seed=args.seed, device=dev, p4=args.p4)
+            for _ in range(args.play):
+                env.step(None)
+            torch.cuda.synchronize()
+            env.check_errors()
+            boards = env.board.clone()
+            host = boards.cpu().numpy()
+            pick = np.random.default_rng(args.seed).choice(n, min(args.sample, n), replace=False)
+            empties = float((host == 0).sum(axis=1).mean())
+            acts = torch.empty(n, dtype=torch.uint8, device=dev)
+            vals = torch.empty((n, 4), dtype=torch.int64, device=dev)
+            calls = [("act", 1, lambda: net.act(boards, q_out=vals, actions_out=acts))]
+            for depth in args.depths:
+                calls.append(("search", depth,
+                              lambda depth=depth: ntsearch.expectimax(
+                                  net, boards, depth, args.p4, values_out=vals, actions_out=acts)))
+            for what, depth, fn in calls:
+                leaves = statistics.fmean(count_leaves(host[i], depth) for i in pick)
+                ms = timed(fn, args.warmup, args.reps)
+                med = statistics.median(ms)
+                row = {"set": name, "table_bytes": net.lut.numel() * 4, "boards": n, "call": what,
+                       "depth": depth, "us_median": med * 1e3, "us_min": min(ms) * 1e3,
+                       "us_max": max(ms) * 1e3, "reps": len(ms), "mean_empty_cells": empties,
+                       "leaves_per_board": leaves, "boards_per_s": n / (med * 1e-3),
+                       "leaves_per_s": n * leaves / (med * 1e-3),
+                       "gathers_per_s": n * leaves * 8 * T / (med * 1e-3)}
+                rows.append(row)
+                print(f"{name} n={n:6d} {what:6s} depth={depth} {row['us_median']:11.1f} us "
+                      f"(min {row['us_min']:.1f}, max {row['us_max']:.1f})  "
+                      f"{row['boards_per_s']:.3e} boards/s  {leaves:9.1f} leaves/board  "
+                      f"{row['leaves_per_s']:.3e} leaves/s  {row['gathers_per_s']:.3e} gathers/s",
+                      flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump({"p4": args.p4, "play": args.play, "lib": args.lib, "rows": rows}, f,
+                      indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -12,7 +12,9 @@
 // xor-shuffles, one floor division finishes the chance node, the four root values are read from
 // lanes 0 / 16 / 32 / 48.  Depth 1 has no chance node and only 4 leaves per board: there a wave
 // takes two boards and the 8 lanes of a move split the leaf, lane 32s + 8a + g gathering
-// symmetry g of after(board s, a) -- the layout of g2048_ntuple.hip's k_policy.
+// symmetry g of after(board s, a) -- the layout of the policy kernels (g2048_ntuple_dev.hpp's
+// policy_lane).  At every depth the greedy move is that header's best_move, with 16 or 8 lanes
+// per move; the index helpers, the host plumbing and the argument checks are its as well.
 //
 // Leaves.  Below the root one lane owns a leaf, so it walks all 8 symmetries itself.  On the
 // packed nibble word (nibble 4r + c = min(b[r][c], 15)) a row flip reverses the four 16-bit
@@ -174,15 +176,12 @@ __device__ __forceinline__ int64_t vmax(const int32_t* __restrict__ lut, const S
 template <uint32_t ROW>
 __device__ __forceinline__ int64_t row_sum(int64_t v) {
     if constexpr (ROW == 16u) v += __shfl_xor(v, 8);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
+    return group_sum(v);
 }
 
 constexpr int BLOCK = 256, WAVES = BLOCK / 64;
 // boards per wave: depth 1 has 4 leaves of 8 symmetries per board, so two boards fill a wave
-// (g2048_ntuple.hip's k_policy layout); deeper searches give a board the whole wave
+// (g2048_ntuple_dev.hpp's policy_lane layout); deeper searches give a board the whole wave
 constexpr int boards_per_wave(int depth) { return depth == 1 ? 2 : 1; }
 
 template <int DEPTH>
@@ -203,7 +202,8 @@ __global__ __launch_bounds__(BLOCK) void k_ntsearch(const int32_t* __restrict__ 
         const uint32_t gain = apply_move(s, a);
         int64_t v;
         if constexpr (DEPTH == 1) {
-            // lane 8a + g gathers symmetry g of the leaf after(b, a): T loads in flight
+            // policy_lane's layout: lane 8a + g gathers symmetry g of the leaf after(b, a), T
+            // loads in flight
             const uint64_t nib = nibbles(sym(s, c));
             const int T = (int)p.nt.n_tuples;
             int32_t e[MAXT];
@@ -229,44 +229,15 @@ __global__ __launch_bounds__(BLOCK) void k_ntsearch(const int32_t* __restrict__ 
             const int32_t ne = __popc(empties(s));
             v = ok ? ((int64_t)gain << F) + floor_div(sum, p.W * max(ne, 1)) : INT64_MIN;
         }
-        const uint32_t base = lane - head;
-        const int64_t v0 = __shfl(v, base), v1 = __shfl(v, base + ROW);
-        const int64_t v2 = __shfl(v, base + 2u * ROW), v3 = __shfl(v, base + 3u * ROW);
-        // smallest a with the largest value; an illegal move holds INT64_MIN and a legal move's
-        // value is far above it, so with no legal move the action stays 0
-        uint32_t act = 0;
-        int64_t best = v0;
-        if (v1 > best) { act = 1; best = v1; }
-        if (v2 > best) { act = 2; best = v2; }
-        if (v3 > best) { act = 3; }
+        const Best m = best_move<ROW>(v, lane);
         if (!live) continue;
         if (values != nullptr && head < 4u)
-            values[i * 4 + head] = head == 0u ? v0 : head == 1u ? v1 : head == 2u ? v2 : v3;
-        if (action != nullptr && head == 0u) action[i] = (uint8_t)act;
+            values[i * 4 + head] = head == 0u ? m.q0 : head == 1u ? m.q1 : head == 2u ? m.q2 : m.q3;
+        if (action != nullptr && head == 0u) action[i] = (uint8_t)m.act;
     }
 }
 
 thread_local std::string g_err;
-
-#define G_HIP(expr)                                                                            \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            refuse(g_err, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return G2048_EHIP;                                                                 \
-        }                                                                                      \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 }  // namespace
 

@@ -3,8 +3,11 @@
 //
 // The rule is defined in include/g2048_nttc.h; every value is an integer and the result is checked
 // bit for bit against tests/nttc_ref.py.  No float anywhere.  The library takes the spec and the
-// table of g2048_ntuple.h and does not link against libg2048_ntuple.so; the index helpers and the
-// argument checks are the shared ones of g2048_ntuple_dev.hpp.
+// table of g2048_ntuple.h and does not link against libg2048_ntuple.so.  What it has in common
+// with g2048_ntuple.hip is g2048_ntuple_dev.hpp's: the index helpers, the policy's lane decode,
+// group sum, argmax and err / delta, the merge table's keys and the prev commit of the update, and
+// the host plumbing and argument checks.  Here are the rate, the (E, A) gather, the hand-over of
+// the steps, the merge table's three sums and the entry points.
 //
 // A step is two launches, because an entry's step depends on its (E, A) from before the call and
 // nothing orders a read in one block against an add in another:
@@ -22,9 +25,7 @@
 //                per sum; lane 0 of the group then commits prev / has_prev.
 // The first launch never writes lut or ea, the second never reads them.
 #include <hip/hip_runtime.h>
-#include <stdarg.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include <string>
 
@@ -44,14 +45,6 @@ using namespace g2048;
 using namespace g2048::nt;
 
 constexpr int RATE_BITS = G2048_NTTC_RATE_BITS;
-
-// sum over the 8 lanes of a group
-__device__ __forceinline__ int64_t group_sum(int64_t v) {
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 1);
-    return v;
-}
 
 // rate(E, A) of the header.  In the domain (|E| <= A < 2^62) both shifted operands are below 2^16
 // and the divisor is at least 1.
@@ -77,25 +70,14 @@ __global__ __launch_bounds__(BLOCK) void k_tc_policy(
     const uint4* __restrict__ prev, const uint8_t* __restrict__ has_prev, int32_t lr_num,
     int32_t lr_shift, int32_t* __restrict__ delta_out, int64_t* __restrict__ err_out,
     int32_t* __restrict__ work, Params p) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const int64_t wave = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    const int64_t i = wave * 2 + (lane >> 5);
-    const uint32_t a = (lane >> 3) & 3u, g = lane & 7u;
-    const bool live = i < n;
-    const int64_t bi = live ? i : n - 1;
-    const Board b = load_board(boards, bi);
-    const uint32_t legal = legal_mask(b);
-    const bool ok = ((legal >> a) & 1u) != 0u;
-    Board s = b;
-    const uint32_t gain = apply_move(s, a);
-    const uint64_t nib = nibbles(sym(s, g));
+    const PolicyLane l = policy_lane<BLOCK>(boards, n);
     int32_t v[T], pv[T];
     longlong2 pea[T];
 #pragma unroll
-    for (int t = 0; t < T; ++t) v[t] = ok ? lut[entry(p, nib, t)] : 0;
-    const bool hp = has_prev[bi] != 0;
-    const bool mine = hp && a == 0u;  // this lane reads idx(prev, g, .)
-    const uint64_t pnib = nibbles(sym(load_board(prev, bi), g));
+    for (int t = 0; t < T; ++t) v[t] = l.ok ? lut[entry(p, l.nib, t)] : 0;
+    const bool hp = has_prev[l.bi] != 0;
+    const bool mine = hp && l.a == 0u;  // this lane reads idx(prev, g, .)
+    const uint64_t pnib = nibbles(sym(load_board(prev, l.bi), l.g));
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const uint32_t e = entry(p, pnib, t);
@@ -106,43 +88,32 @@ __global__ __launch_bounds__(BLOCK) void k_tc_policy(
 #pragma unroll
     for (int t = 0; t < T; ++t) sum += v[t];
     sum = group_sum(sum);
-    const int64_t q = ok ? ((int64_t)gain << F) + sum : INT64_MIN;
-    const uint32_t base = lane & 32u;
-    const int64_t q0 = __shfl(q, base), q1 = __shfl(q, base + 8u);
-    const int64_t q2 = __shfl(q, base + 16u), q3 = __shfl(q, base + 24u);
-    // smallest a with the largest q; an illegal move holds INT64_MIN and a legal move's q is far
-    // above it, so with no legal move the action stays 0
-    uint32_t act = 0;
-    int64_t best = q0;
-    if (q1 > best) { act = 1; best = q1; }
-    if (q2 > best) { act = 2; best = q2; }
-    if (q3 > best) { act = 3; best = q3; }
+    const Best m = best_move<8>(l.ok ? ((int64_t)l.gain << F) + sum : INT64_MIN, l.lane);
 #pragma unroll
     for (int t = 0; t < T; ++t) psum += pv[t];
     psum = group_sum(psum);  // V(prev) in the group a == 0
-    if (!live) return;
+    if (!l.live) return;
     // every lane of the group a == 0 holds best, V(prev) and has_prev: err and delta need no
     // broadcast
-    const int64_t target = legal != 0u ? best : 0;
-    const int64_t err = hp ? target - psum : 0;
-    const int32_t delta = (int32_t)((err * (int64_t)lr_num) >> lr_shift);
-    if ((lane & 31u) == 0u) {
-        action_out[i] = (uint8_t)act;
-        delta_out[i] = delta;
-        if (err_out != nullptr) err_out[i] = err;
+    const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
+    if ((l.lane & 31u) == 0u) {
+        action_out[l.i] = (uint8_t)m.act;
+        delta_out[l.i] = td.delta;
+        if (err_out != nullptr) err_out[l.i] = td.err;
     }
-    if (mine && delta != 0) {
-        int32_t* w = work + (i * 8 + g) * T;
+    if (mine && td.delta != 0) {
+        int32_t* w = work + (l.i * 8 + l.g) * T;
 #pragma unroll
-        for (int t = 0; t < T; ++t) w[t] = tc_step_of(delta, tc_rate(pea[t].x, pea[t].y));
+        for (int t = 0; t < T; ++t) w[t] = tc_step_of(td.delta, tc_rate(pea[t].x, pea[t].y));
     }
 }
 
 // The update's block: 128 boards.  The boards of a batch share their early-game entries, and adds
 // into one address serialise at the memory side, so a block first sums what it adds into an entry
-// in an LDS hash table (the entry index is the key; after four slots taken by other keys the adds
-// go straight to memory) and then flushes every used slot.  Integer adds commute and associate
-// modulo 2^32 and 2^64, so lut and ea end up the same whichever way the sums are grouped.
+// in an LDS hash table (g2048_ntuple_dev.hpp's clear_keys / claim_slot: the entry index is the
+// key; after four slots taken by other keys the adds go straight to memory) and then flushes every
+// used slot.  Integer adds commute and associate modulo 2^32 and 2^64, so lut and ea end up the
+// same whichever way the sums are grouped.
 constexpr int UBLOCK = 1024;
 #if G2048_NTTC_MERGE
 // log2 of the table's slots; a slot is 24 bytes (key, step sum, E sum, A sum) and a block makes
@@ -157,8 +128,6 @@ constexpr int slot_bits() {
     return T <= 1 ? 9 : T == 2 ? 10 : 12;
 #endif
 }
-constexpr uint32_t PROBES = 4;           // linear probing
-constexpr uint32_t NO_KEY = 0xFFFFFFFFu;  // entry indices are < 2^27
 #endif
 
 using u64 = unsigned long long;
@@ -185,8 +154,8 @@ __global__ __launch_bounds__(UBLOCK) void k_tc_update(
     __shared__ uint32_t steps[SLOTS];
     __shared__ u64 esum[SLOTS];
     __shared__ u64 asum[SLOTS];
+    clear_keys<SLOT_BITS, UBLOCK>(keys);
     for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
-        keys[s] = NO_KEY;
         steps[s] = 0u;
         esum[s] = 0ull;
         asum[s] = 0ull;
@@ -213,21 +182,14 @@ __global__ __launch_bounds__(UBLOCK) void k_tc_update(
             const uint32_t e = entry(p, nib, t);
             const uint32_t step = (uint32_t)st[t];
 #if G2048_NTTC_MERGE
-            const uint32_t home = (e * 0x9E3779B1u) >> (32 - SLOT_BITS);
-            bool placed = false;
-#pragma unroll
-            for (uint32_t probe = 0; probe < PROBES; ++probe) {
-                if (placed) continue;
-                const uint32_t slot = (home + probe) & (SLOTS - 1u);
-                const uint32_t old = atomicCAS(&keys[slot], NO_KEY, e);
-                placed = old == NO_KEY || old == e;
-                if (placed) {
-                    if (step != 0u) atomicAdd(&steps[slot], step);
-                    atomicAdd(&esum[slot], de);
-                    atomicAdd(&asum[slot], da);
-                }
+            const uint32_t slot = claim_slot<SLOT_BITS>(keys, e);
+            if (slot != NO_SLOT) {
+                if (step != 0u) atomicAdd(&steps[slot], step);
+                atomicAdd(&esum[slot], de);
+                atomicAdd(&asum[slot], da);
+            } else {
+                add_entry(table, ea, e, step, de, da);
             }
-            if (!placed) add_entry(table, ea, e, step, de, da);
 #else
             add_entry(table, ea, e, step, de, da);
 #endif
@@ -241,63 +203,10 @@ __global__ __launch_bounds__(UBLOCK) void k_tc_update(
         if (k != NO_KEY) add_entry(table, ea, k, steps[s], esum[s], asum[s]);
     }
 #endif
-    if (!live || g != 0u) return;
-    const Board b = load_board(boards, i);
-    const bool any = legal_mask(b) != 0u;
-    if (any) {
-        Board s = b;
-        apply_move(s, (uint32_t)action[i] & 3u);
-        prev[i] = make_uint4(s.r0, s.r1, s.r2, s.r3);
-    }
-    has_prev[i] = any ? 1 : 0;
+    if (live && g == 0u) commit_prev(boards, i, action, prev, has_prev);
 }
 
 thread_local std::string g_err;
-
-int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define G_HIP(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(G2048_EHIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                        __LINE__);                                                         \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev);
-        else prev = -1;
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-#define DISPATCH_T(T_, CALL)                       \
-    switch (T_) {                                  \
-    case 1: { constexpr int TT = 1; CALL; } break; \
-    case 2: { constexpr int TT = 2; CALL; } break; \
-    case 3: { constexpr int TT = 3; CALL; } break; \
-    case 4: { constexpr int TT = 4; CALL; } break; \
-    case 5: { constexpr int TT = 5; CALL; } break; \
-    case 6: { constexpr int TT = 6; CALL; } break; \
-    case 7: { constexpr int TT = 7; CALL; } break; \
-    default: { constexpr int TT = 8; CALL; } break; \
-    }
-
-// blocks for n boards at `per` boards per block
-dim3 grid_for(int64_t n, int per) { return dim3((uint32_t)((n + per - 1) / per)); }
 
 }  // namespace
 
@@ -307,10 +216,10 @@ const char* g2048_nttc_last_error(void) { return g_err.c_str(); }
 
 int32_t g2048_nttc_rate(int64_t E, int64_t A) {
     if (A < 0 || A > G2048_NTTC_MAX_A)
-        return fail(G2048_EINVAL, "nttc_rate: A = %lld outside [0, 2^62)", (long long)A);
+        return refuse(g_err, "nttc_rate: A = %lld outside [0, 2^62)", (long long)A);
     if (E > A || E < -A)
-        return fail(G2048_EINVAL, "nttc_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
-                    (long long)A);
+        return refuse(g_err, "nttc_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
+                      (long long)A);
     return (int32_t)tc_rate(E, A);
 }
 
@@ -318,8 +227,8 @@ int64_t g2048_nttc_work_bytes(const g2048_ntuple_spec* spec, int64_t n) {
     const int rc = nt::check_spec(g_err, "nttc_work_bytes", spec);
     if (rc != G2048_OK) return rc;
     if (n < 1 || n > G2048_MAX_BOARDS)
-        return fail(G2048_EINVAL, "nttc_work_bytes: n = %lld outside [1, G2048_MAX_BOARDS]",
-                    (long long)n);
+        return refuse(g_err, "nttc_work_bytes: n = %lld outside [1, G2048_MAX_BOARDS]",
+                      (long long)n);
     return n * 8 * spec->n_tuples * (int64_t)sizeof(int32_t);
 }
 
@@ -328,30 +237,18 @@ int g2048_nttc_step(const g2048_ntuple_spec* spec, int32_t* lut_dev, int64_t* ea
                     int32_t lr_num, int32_t lr_shift, uint8_t* action_out_dev,
                     int32_t* delta_out_dev, int64_t* err_out_dev, void* work_dev, int device_id,
                     void* stream) {
-    const int rc = nt::check_common(g_err, "nttc_step", spec, lut_dev, boards_dev, n);
+    const char* who = "nttc_step";
+    int rc = check_common(g_err, who, spec, lut_dev, boards_dev, n);
     if (rc != G2048_OK) return rc;
-    if (ea_dev == nullptr) return fail(G2048_EINVAL, "nttc_step: ea_dev is NULL");
+    if (ea_dev == nullptr) return refuse(g_err, "nttc_step: ea_dev is NULL");
     if (((uintptr_t)ea_dev & 15u) != 0)
-        return fail(G2048_EINVAL, "nttc_step: ea_dev must be 16-byte aligned");
-    if (prev_dev == nullptr || has_prev_dev == nullptr)
-        return fail(G2048_EINVAL, "nttc_step: prev_dev / has_prev_dev is NULL");
-    if (((uintptr_t)prev_dev & 15u) != 0)
-        return fail(G2048_EINVAL, "nttc_step: prev_dev must be 16-byte aligned");
-    if (lr_num < 0 || lr_num > G2048_NTUPLE_MAX_LR_NUM)
-        return fail(G2048_EINVAL, "nttc_step: lr_num = %d outside [0, %d]", lr_num,
-                    G2048_NTUPLE_MAX_LR_NUM);
-    if (lr_shift < 0 || lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
-        return fail(G2048_EINVAL, "nttc_step: lr_shift = %d outside [0, %d]", lr_shift,
-                    G2048_NTUPLE_MAX_LR_SHIFT);
-    if (action_out_dev == nullptr || delta_out_dev == nullptr)
-        return fail(G2048_EINVAL, "nttc_step: action_out_dev / delta_out_dev is NULL");
-    if (((uintptr_t)delta_out_dev & 3u) != 0)
-        return fail(G2048_EINVAL, "nttc_step: delta_out_dev must be 4-byte aligned");
-    if (((uintptr_t)err_out_dev & 7u) != 0)
-        return fail(G2048_EINVAL, "nttc_step: err_out_dev must be 8-byte aligned");
-    if (work_dev == nullptr) return fail(G2048_EINVAL, "nttc_step: work_dev is NULL");
+        return refuse(g_err, "nttc_step: ea_dev must be 16-byte aligned");
+    rc = check_td_args(g_err, who, prev_dev, has_prev_dev, lr_num, lr_shift, action_out_dev,
+                       delta_out_dev, err_out_dev);
+    if (rc != G2048_OK) return rc;
+    if (work_dev == nullptr) return refuse(g_err, "nttc_step: work_dev is NULL");
     if (((uintptr_t)work_dev & 3u) != 0)
-        return fail(G2048_EINVAL, "nttc_step: work_dev must be 4-byte aligned");
+        return refuse(g_err, "nttc_step: work_dev must be 4-byte aligned");
     const Params p = make_params(*spec);
     DeviceGuard guard(device_id);
     hipStream_t st = (hipStream_t)stream;

@@ -1,9 +1,16 @@
-// g2048_ntuple_dev.hpp -- what the two libraries that read an n-tuple table share
-// (g2048_ntuple.hip -> libg2048_ntuple.so, g2048_ntsearch.hip -> libg2048_ntsearch.so): the
-// device helpers that turn a board into table indices (include/g2048_ntuple.h: symmetries, the
-// clamp to 15, idx) and the host-side validation of a spec and of the arguments every device
-// entry point has.  Header-only and internal to each library: nothing here is exported, and the
-// libraries do not link against each other.
+// g2048_ntuple_dev.hpp -- the one internal header of the n-tuple family: what g2048_ntuple.hip
+// (libg2048_ntuple.so), g2048_ntsearch.hip (libg2048_ntsearch.so) and g2048_nttc.hip
+// (libg2048_nttc.so) share.
+//   device  board -> table indices (include/g2048_ntuple.h: symmetries, the clamp to 15, idx);
+//           the afterstate policy's lane layout 32s + 8a + g (policy_lane), the sum over a group
+//           (group_sum), the argmax over the four moves (best_move), err and delta (td_error);
+//           the update kernels' LDS merge table (clear_keys, claim_slot) and their common tail
+//           (commit_prev).  The gathers and the payload of the merge table stay in the kernels.
+//   host    the error writer (refuse), G_HIP, DeviceGuard, DISPATCH_T, grid_for, and the
+//           validation of a spec, of the arguments every device entry point has and of those
+//           the two learning steps share (check_spec, check_common, check_td_args).
+// Header-only and internal to each library: nothing here is exported, and the libraries do not
+// link against each other.  Each .hip keeps its own thread_local g_err, which G_HIP writes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -78,7 +85,130 @@ __device__ __forceinline__ Board load_board(const uint4* p, int64_t i) {
     return Board{w.x, w.y, w.z, w.w};
 }
 
-// ------------------------------------------------------------------ host: validation
+// sum over the 8 lanes of a group
+__device__ __forceinline__ int64_t group_sum(int64_t v) {
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 1);
+    return v;
+}
+
+// ------------------------------------------------------------------ device: afterstate policy
+// The policy kernels' lane: 2 boards per wave, lane 32s + 8a + g holds after(board s, a) under
+// symmetry g.  A dead half-wave (i >= n) keeps its lanes for the shuffles and reads board n - 1.
+struct PolicyLane {
+    int64_t i, bi;       // the board; the board read (bi = i where live)
+    uint32_t lane, a, g;
+    bool live, ok;       // i < n; move a is legal
+    uint32_t legal, gain;
+    Board b, s;          // the board and after(b, a)
+    uint64_t nib;        // nibbles(g(s))
+};
+
+template <int BLOCK>
+__device__ __forceinline__ PolicyLane policy_lane(const uint4* __restrict__ boards, int64_t n) {
+    PolicyLane l;
+    l.lane = threadIdx.x & 63u;
+    const int64_t wave = (int64_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    l.i = wave * 2 + (l.lane >> 5);
+    l.a = (l.lane >> 3) & 3u;
+    l.g = l.lane & 7u;
+    l.live = l.i < n;
+    l.bi = l.live ? l.i : n - 1;
+    l.b = load_board(boards, l.bi);
+    l.legal = legal_mask(l.b);
+    l.ok = ((l.legal >> l.a) & 1u) != 0u;
+    l.s = l.b;
+    l.gain = apply_move(l.s, l.a);
+    l.nib = nibbles(sym(l.s, l.g));
+    return l;
+}
+
+// The four moves' values and the greedy move, from the value q of this lane's move.  A move has
+// ROW lanes (8: two boards per wave, 16: one), move a's value is read from the first of them.
+// The smallest a with the largest q wins; an illegal move holds INT64_MIN and a legal move's q is
+// far above it, so with no legal move the action stays 0.
+struct Best {
+    int64_t q0, q1, q2, q3, best;
+    uint32_t act;
+};
+
+template <uint32_t ROW>
+__device__ __forceinline__ Best best_move(int64_t q, uint32_t lane) {
+    const uint32_t base = lane & ~(4u * ROW - 1u);
+    Best m;
+    m.q0 = __shfl(q, base), m.q1 = __shfl(q, base + ROW);
+    m.q2 = __shfl(q, base + 2u * ROW), m.q3 = __shfl(q, base + 3u * ROW);
+    m.act = 0;
+    m.best = m.q0;
+    if (m.q1 > m.best) { m.act = 1; m.best = m.q1; }
+    if (m.q2 > m.best) { m.act = 2; m.best = m.q2; }
+    if (m.q3 > m.best) { m.act = 3; m.best = m.q3; }
+    return m;
+}
+
+// err and delta of the learning steps: the target is the best q (0 on a terminal board), and a
+// board without a previous afterstate learns nothing
+struct TdError {
+    int64_t err;
+    int32_t delta;
+};
+
+__device__ __forceinline__ TdError td_error(int64_t best, int64_t psum, bool hp, uint32_t legal,
+                                            int32_t lr_num, int32_t lr_shift) {
+    const int64_t target = legal != 0u ? best : 0;
+    const int64_t err = hp ? target - psum : 0;
+    return TdError{err, (int32_t)((err * (int64_t)lr_num) >> lr_shift)};
+}
+
+// ------------------------------------------------------------------ device: update kernels
+// The LDS merge table in front of the atomics: the entry index is the key of an open-addressed
+// table of 2^SLOT_BITS slots, linear probing.  Each kernel keeps its payload arrays beside `keys`
+// and adds into the slot it claimed; after PROBES slots taken by other keys the add goes straight
+// to memory.
+constexpr uint32_t PROBES = 4;
+constexpr uint32_t NO_KEY = 0xFFFFFFFFu;  // entry indices are < 2^27
+// slots are < 2^13; that it equals NO_KEY is a coincidence, the two are never compared
+constexpr uint32_t NO_SLOT = 0xFFFFFFFFu;
+constexpr uint32_t HASH_MUL = 0x9E3779B1u;  // 2^32 / golden ratio (Fibonacci hashing)
+
+// every slot free; a block of THREADS threads (the caller's barrier follows)
+template <int SLOT_BITS, int THREADS>
+__device__ __forceinline__ void clear_keys(uint32_t* keys) {
+    for (uint32_t s = threadIdx.x; s < (1u << SLOT_BITS); s += THREADS) keys[s] = NO_KEY;
+}
+
+// the slot that holds key e, claimed if it was free; NO_SLOT after PROBES slots of other keys
+template <int SLOT_BITS>
+__device__ __forceinline__ uint32_t claim_slot(uint32_t* keys, uint32_t e) {
+    const uint32_t home = (e * HASH_MUL) >> (32 - SLOT_BITS);
+#pragma unroll
+    for (uint32_t probe = 0; probe < PROBES; ++probe) {
+        const uint32_t slot = (home + probe) & ((1u << SLOT_BITS) - 1u);
+        const uint32_t old = atomicCAS(&keys[slot], NO_KEY, e);
+        if (old == NO_KEY || old == e) return slot;
+    }
+    return NO_SLOT;
+}
+
+// The update kernels' tail, for lane 0 of a live board's group: prev <- after(board, action) and
+// has_prev <- 1, or has_prev <- 0 on a terminal board.  The caller puts a barrier between its
+// last read of prev[i] / has_prev[i] and this.
+__device__ __forceinline__ void commit_prev(const uint4* __restrict__ boards, int64_t i,
+                                            const uint8_t* __restrict__ action,
+                                            uint4* __restrict__ prev,
+                                            uint8_t* __restrict__ has_prev) {
+    const Board b = load_board(boards, i);
+    const bool any = legal_mask(b) != 0u;
+    if (any) {
+        Board s = b;
+        apply_move(s, (uint32_t)action[i] & 3u);
+        prev[i] = make_uint4(s.r0, s.r1, s.r2, s.r3);
+    }
+    has_prev[i] = any ? 1 : 0;
+}
+
+// ------------------------------------------------------------------ host: errors and launches
 // Each library keeps its own thread-local message; these write the reason into `err`.
 inline int refuse(std::string& err, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 inline int refuse(std::string& err, const char* fmt, ...) {
@@ -90,6 +220,47 @@ inline int refuse(std::string& err, const char* fmt, ...) {
     err = buf;
     return G2048_EINVAL;
 }
+
+// a failed HIP call: its text into g_err, G2048_EHIP to the caller.  Requires a std::string
+// named g_err in scope where it is used: each including .hip defines its own thread_local one.
+#define G_HIP(expr)                                                                            \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) {                                                                \
+            ::g2048::nt::refuse(g_err, "%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
+                                __LINE__);                                                     \
+            return G2048_EHIP;                                                                 \
+        }                                                                                      \
+    } while (0)
+
+struct DeviceGuard {
+    int prev = -1;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) (void)hipSetDevice(dev);
+        else prev = -1;
+    }
+    ~DeviceGuard() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+// CALL with the tuple count as the constant TT (a checked spec has 1..8 tuples)
+#define DISPATCH_T(T_, CALL)                       \
+    switch (T_) {                                  \
+    case 1: { constexpr int TT = 1; CALL; } break; \
+    case 2: { constexpr int TT = 2; CALL; } break; \
+    case 3: { constexpr int TT = 3; CALL; } break; \
+    case 4: { constexpr int TT = 4; CALL; } break; \
+    case 5: { constexpr int TT = 5; CALL; } break; \
+    case 6: { constexpr int TT = 6; CALL; } break; \
+    case 7: { constexpr int TT = 7; CALL; } break; \
+    default: { constexpr int TT = 8; CALL; } break; \
+    }
+
+// blocks for n boards at `per` boards per block
+inline dim3 grid_for(int64_t n, int per) { return dim3((uint32_t)((n + per - 1) / per)); }
+
+// ------------------------------------------------------------------ host: validation
 
 inline int check_spec(std::string& err, const char* who, const g2048_ntuple_spec* spec) {
     if (spec == nullptr) return refuse(err, "%s: spec is NULL", who);
@@ -134,6 +305,30 @@ inline int check_common(std::string& err, const char* who, const g2048_ntuple_sp
         return refuse(err, "%s: boards_dev must be 16-byte aligned", who);
     if (n < 1 || n > G2048_MAX_BOARDS)
         return refuse(err, "%s: n = %lld outside [1, G2048_MAX_BOARDS]", who, (long long)n);
+    return G2048_OK;
+}
+
+// the checks g2048_ntuple_td_step and g2048_nttc_step share past check_common
+inline int check_td_args(std::string& err, const char* who, const uint8_t* prev,
+                         const uint8_t* has_prev, int32_t lr_num, int32_t lr_shift,
+                         const uint8_t* action_out, const int32_t* delta_out,
+                         const int64_t* err_out) {
+    if (prev == nullptr || has_prev == nullptr)
+        return refuse(err, "%s: prev_dev / has_prev_dev is NULL", who);
+    if (((uintptr_t)prev & 15u) != 0)
+        return refuse(err, "%s: prev_dev must be 16-byte aligned", who);
+    if (lr_num < 0 || lr_num > G2048_NTUPLE_MAX_LR_NUM)
+        return refuse(err, "%s: lr_num = %d outside [0, %d]", who, lr_num,
+                      G2048_NTUPLE_MAX_LR_NUM);
+    if (lr_shift < 0 || lr_shift > G2048_NTUPLE_MAX_LR_SHIFT)
+        return refuse(err, "%s: lr_shift = %d outside [0, %d]", who, lr_shift,
+                      G2048_NTUPLE_MAX_LR_SHIFT);
+    if (action_out == nullptr || delta_out == nullptr)
+        return refuse(err, "%s: action_out_dev / delta_out_dev is NULL", who);
+    if (((uintptr_t)delta_out & 3u) != 0)
+        return refuse(err, "%s: delta_out_dev must be 4-byte aligned", who);
+    if (((uintptr_t)err_out & 7u) != 0)
+        return refuse(err, "%s: err_out_dev must be 8-byte aligned", who);
     return G2048_OK;
 }
 

@@ -134,18 +134,25 @@ class NativeError(RuntimeError):
     pass
 
 
+def bind(path: str, signatures: dict) -> C.CDLL:
+    """Open the library at `path` and set restype / argtypes of every symbol in `signatures`
+    (name -> (restype, argtypes)); the load() of each library's module calls this."""
+    if not os.path.exists(path):
+        raise ImportError(f"{path} is not built: run `python -c 'import __graft_entry__ as g; "
+                          "g.build()'` (hipcc --offload-arch=gfx950)")
+    lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    return lib
+
+
 def load() -> C.CDLL:
     """Load libg2048.so and bind every declared symbol (no GPU needed for this)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as g; "
-                              "g.build()'` (hipcc --offload-arch=gfx950)")
-        lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
+        lib = bind(LIB_PATH, SIGNATURES)
         if lib.g2048_abi_version() != ABI_VERSION:
             raise ImportError("libg2048.so ABI version mismatch")
         _lib = lib

@@ -41,15 +41,7 @@ def load() -> C.CDLL:
     """Load libg2048_ntsearch.so and bind its symbols (no GPU needed for this)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as "
-                              "g; g.build()'` (hipcc --offload-arch=gfx950)")
-        lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
+        _lib = N.bind(LIB_PATH, SIGNATURES)
     return _lib
 
 

@@ -50,15 +50,7 @@ def load() -> C.CDLL:
     """Load libg2048_nttc.so and bind its symbols (no GPU needed for this)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as "
-                              "g; g.build()'` (hipcc --offload-arch=gfx950)")
-        lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
+        _lib = N.bind(LIB_PATH, SIGNATURES)
     return _lib
 
 
@@ -101,15 +93,7 @@ class TCState:
         device tensor of at least work_bytes(spec, n); without one it is allocated here."""
         net = self.net
         dev = net._gpu()
-        n = NT._boards(boards, dev)
-        NT._boards(prev, dev)
-        for t, dt, shape in ((prev, torch.uint8, (n, 16)), (has_prev, torch.uint8, (n,)),
-                             (actions_out, torch.uint8, (n,)), (delta_out, torch.int32, (n,))):
-            if t is None:
-                raise ValueError("tc_step needs prev, has_prev, actions_out and delta_out")
-            NT._out(t, dt, shape, dev)
-        if err_out is not None:
-            NT._out(err_out, torch.int64, (n,), dev)
+        n = NT._step_args("tc_step", boards, prev, has_prev, actions_out, delta_out, err_out, dev)
         need = work_bytes(net.spec, n)
         if work is None:
             work = torch.empty(need, dtype=torch.uint8, device=dev)

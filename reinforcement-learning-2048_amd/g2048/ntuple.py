@@ -67,15 +67,7 @@ def load() -> C.CDLL:
     """Load libg2048_ntuple.so and bind its symbols (no GPU needed for this)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(f"{LIB_PATH} is not built: run `python -c 'import __graft_entry__ as "
-                              "g; g.build()'` (hipcc --offload-arch=gfx950)")
-        lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = lib
+        _lib = N.bind(LIB_PATH, SIGNATURES)
     return _lib
 
 
@@ -158,6 +150,20 @@ def _out(t, dtype, shape, dev):
     return t
 
 
+def _step_args(who, boards, prev, has_prev, actions_out, delta_out, err_out, dev) -> int:
+    """The tensors td_step and tc_step (`who`) share, validated; returns n."""
+    n = _boards(boards, dev)
+    _boards(prev, dev)
+    for t, dt, shape in ((prev, torch.uint8, (n, 16)), (has_prev, torch.uint8, (n,)),
+                         (actions_out, torch.uint8, (n,)), (delta_out, torch.int32, (n,))):
+        if t is None:
+            raise ValueError(f"{who} needs prev, has_prev, actions_out and delta_out")
+        _out(t, dt, shape, dev)
+    if err_out is not None:
+        _out(err_out, torch.int64, (n,), dev)
+    return n
+
+
 class NTupleNetwork:
     """The table of one spec: `lut` int32 [T, 16^m], zero-initialised.  On a GPU device it
     evaluates and acts through the library; on the CPU it only holds, saves and loads the table."""
@@ -216,15 +222,7 @@ class NTupleNetwork:
                 err_out=None):
         """One TD(0) step of the header on caller-owned state and outputs (no allocation)."""
         dev = self._gpu()
-        n = _boards(boards, dev)
-        _boards(prev, dev)
-        for t, dt, shape in ((prev, torch.uint8, (n, 16)), (has_prev, torch.uint8, (n,)),
-                             (actions_out, torch.uint8, (n,)), (delta_out, torch.int32, (n,))):
-            if t is None:
-                raise ValueError("td_step needs prev, has_prev, actions_out and delta_out")
-            _out(t, dt, shape, dev)
-        if err_out is not None:
-            _out(err_out, torch.int64, (n,), dev)
+        n = _step_args("td_step", boards, prev, has_prev, actions_out, delta_out, err_out, dev)
         with torch.cuda.device(dev):
             check(load().g2048_ntuple_td_step(
                 C.byref(self._c), N.ptr(self.lut), N.ptr(boards), n, N.ptr(prev),

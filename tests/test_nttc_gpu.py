@@ -184,6 +184,24 @@ def test_tc_step_under_heavy_collisions(M):
     run.env.check_errors()
 
 
+@pytest.mark.parametrize("T", range(1, 9))
+def test_tc_step_at_every_tuple_count(M, T):
+    """Every instantiation of the policy and update kernels (T = 1..8, the first T tuples of
+    T8M3): 131 boards -- two update blocks, an odd count, a dead half-wave in the policy kernel --
+    3 steps from reset boards.  Step 0 has no previous afterstate and adds nothing; the later
+    steps add into the few early-game entries all boards share.  Table, accumulators, prev,
+    has_prev, actions, err and delta equal the reference after every step."""
+    net = random_table(M, T8M3[:T], 50 + T)
+    run = Run(M, net, 131, seed=46, lr_num=3, lr_shift=6)
+    run.step(0)
+    assert not run.ref.A and not run.ref.net.touched and run.ref_has == [1] * 131
+    for t in (1, 2):
+        run.step(t)
+    adds = 2 * 8 * T * 131  # (board, g, t) triples that added, at most
+    assert 0 < len(run.ref.A) < adds // 4 and {k[0] for k in run.ref.A} == set(range(T))
+    run.env.check_errors()
+
+
 # ------------------------------------------------------------------ 2. the shift path
 def test_tc_step_rate_shift_path_on_preloaded_accumulators(M):
     """The 2x4 set, 64 boards, one step on accumulators preloaded with seeded in-domain values:

@@ -402,6 +402,24 @@ def test_td_step_with_more_entries_than_the_block_can_merge(NT):
     assert torch.equal(net2.lut, net.lut) and out_d.cpu().tolist() == deltas
 
 
+@pytest.mark.parametrize("T", range(1, 9))
+def test_td_step_at_every_tuple_count(NT, T):
+    """Every instantiation of the policy and update kernels (T = 1..8, the first T tuples of
+    T8M3): 131 boards -- two update blocks, an odd count, a dead half-wave in the policy kernel --
+    3 steps from reset boards.  Step 0 has no previous afterstate and adds nothing; the later
+    steps add into the few early-game entries all boards share.  Table, prev, has_prev, actions,
+    err and delta equal the reference after every step."""
+    net = random_table(NT, T8M3[:T], 50 + T)
+    run = Run(NT, net, 131, seed=46, lr_num=3, lr_shift=6)
+    run.step(0)
+    assert not run.ref.touched and run.ref_has == [1] * 131
+    for t in (1, 2):
+        run.step(t)
+    adds = 2 * 8 * T * 131  # (board, g, t) triples that added, at most
+    assert 0 < len(run.ref.touched) < adds // 4 and {k[0] for k in run.ref.touched} == set(range(T))
+    run.env.check_errors()
+
+
 # ------------------------------------------------------------------ 6. order-free
 def test_two_identical_runs_give_equal_tables(NT):
     def run():

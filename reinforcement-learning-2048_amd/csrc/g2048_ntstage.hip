@@ -1,0 +1,404 @@
+// g2048_ntstage.hip -- multi-stage n-tuple value network with weight promotion for gfx950
+// (libg2048_ntstage.so): evaluation, greedy afterstate policy and the TD(0) update.
+//
+// The network is defined in include/g2048_ntstage.h: S tables of g2048_ntuple.h's shape, the one
+// a board reads chosen by its largest tile, and INT32_MIN for "never written", which falls
+// through to the stage below.  Every value is an integer and the result is checked bit for bit
+// against tests/ntstage_ref.py.  No float anywhere.
+//
+// The kernels keep the frames of g2048_ntuple.hip (lane layouts, group sum, argmax, err / delta,
+// the LDS merge table and the prev commit all come from g2048_ntuple_dev.hpp):
+//   k_stage_values  8 boards per wave (one group each)
+//   k_stage_policy  2 boards per wave: lane 32s + 8a + g evaluates after(board s, a) under g, at
+//                   the AFTERSTATE's stage.  For the TD step the groups a == 0 also gather
+//                   V(prev) in the same burst and store the promoted values.
+//   k_stage_update  8 boards per wave, 128 per block: lane g adds delta into its T entries of
+//                   idx(prev, g, .) at stage(prev) through the block's LDS merge table.
+// What is new:
+//   M(b) and the stage  M(b) is taken on the un-transformed board in registers: the even and the
+//       odd bytes of the four words as 16-bit pairs, seven v_pk_max_u16 and one max of the two
+//       halves.  The bounds ride in the params struct as eight bytes (255 past S - 1, above any
+//       exponent), wave-uniform, so the stage is seven compares against scalar operands.  The
+//       entry index becomes s * T * 16^m + entry(...) < 2^30, so NO_KEY stays free.
+//   Gathers  The T gathers at the lane's own stage are all issued before the first use.  Lanes
+//       that received UNSET then step down one stage and gather again, at most S - 1 rounds and
+//       only the lanes that need it; a wave leaves the loop as soon as none of its lanes does.
+//       In the TD step the afterstate's and prev's entries share the rounds.
+//   Promotion  The groups a == 0 of the policy launch have resolved prev's entries; they store
+//       the resolved value into those they found UNSET.  Every word that launch writes is an
+//       UNSET entry, and what is written is the value the entry resolves to in the pre-call
+//       table, so any other lane that reads it, before or after the store, resolves to the same
+//       number, and two lanes that promote one entry store the same number.  Nothing has to be
+//       ordered inside the launch.  The update launch then only adds, into entries that are no
+//       longer UNSET, and never reads the table.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <type_traits>
+
+#include "../../include/g2048_ntstage.h"
+#include "../../include/g2048_ntuple.h"
+#include "g2048_board.hpp"
+#include "g2048_ntuple_dev.hpp"
+
+namespace {
+
+using namespace g2048;
+using namespace g2048::nt;
+
+constexpr int BLOCK = 256;
+constexpr int MAXS = G2048_NTSTAGE_MAX_STAGES;
+constexpr int32_t UNSET = G2048_NTSTAGE_UNSET;
+
+struct StageParams {
+    uint32_t stride;    // T * 16^m, the entries of one stage
+    uint32_t n_stages;  // S
+    uint64_t bounds;    // byte k = bounds[k] for k < S - 1, 255 (above any exponent) past that
+};
+
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ u16x2 pairs(uint32_t w) { return __builtin_bit_cast(u16x2, w); }
+
+// M(b): the largest exponent byte.  Even and odd bytes as 16-bit pairs, a packed max over the
+// eight words, then the larger half.
+__device__ __forceinline__ uint32_t max_tile(const Board& b) {
+    constexpr uint32_t EVEN = 0x00FF00FFu;
+    u16x2 m = __builtin_elementwise_max(pairs(b.r0 & EVEN), pairs((b.r0 >> 8) & EVEN));
+    m = __builtin_elementwise_max(m, pairs(b.r1 & EVEN));
+    m = __builtin_elementwise_max(m, pairs((b.r1 >> 8) & EVEN));
+    m = __builtin_elementwise_max(m, pairs(b.r2 & EVEN));
+    m = __builtin_elementwise_max(m, pairs((b.r2 >> 8) & EVEN));
+    m = __builtin_elementwise_max(m, pairs(b.r3 & EVEN));
+    m = __builtin_elementwise_max(m, pairs((b.r3 >> 8) & EVEN));
+    const uint32_t w = __builtin_bit_cast(uint32_t, m);
+    return max(w & 0xFFFFu, w >> 16);
+}
+
+// stage(b): the number of bounds that M(b) reaches
+__device__ __forceinline__ uint32_t stage_of(const Board& b, const StageParams& sp) {
+    const uint32_t m = max_tile(b);
+    uint32_t s = 0;
+#pragma unroll
+    for (int k = 0; k < MAXS - 1; ++k) s += m >= ((uint32_t)(sp.bounds >> (8 * k)) & 0xFFu) ? 1u : 0u;
+    return s;
+}
+
+// The fall-through: v[t] holds lut[e[t]] of a lane at stage s (0 in a lane that gathers
+// nothing).  Round r reads the entry r stages down for every value still UNSET in a lane with
+// s >= r; what is UNSET at stage 0 is 0.  With TWO a second set (pe, pv, ps) shares the rounds.
+// Called by whole waves: the loop's exit is a wave vote.
+template <int T, bool TWO, typename LUT>
+__device__ __forceinline__ void resolve(LUT lut, const StageParams& sp, const uint32_t (&e)[T],
+                                        int32_t (&v)[T], uint32_t s, const uint32_t (&pe)[T],
+                                        int32_t (&pv)[T], uint32_t ps) {
+    for (uint32_t r = 1; r < sp.n_stages; ++r) {
+        bool need = false;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            need |= v[t] == UNSET && s >= r;
+            if constexpr (TWO) need |= pv[t] == UNSET && ps >= r;
+        }
+        if (!__any(need)) break;
+        const uint32_t down = r * sp.stride;
+        int32_t w[T], pw[T];
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            w[t] = (v[t] == UNSET && s >= r) ? lut[e[t] - down] : v[t];
+            if constexpr (TWO) pw[t] = (pv[t] == UNSET && ps >= r) ? lut[pe[t] - down] : pv[t];
+        }
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            v[t] = w[t];
+            if constexpr (TWO) pv[t] = pw[t];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        v[t] = v[t] == UNSET ? 0 : v[t];
+        if constexpr (TWO) pv[t] = pv[t] == UNSET ? 0 : pv[t];
+    }
+}
+
+template <int T>
+__global__ __launch_bounds__(BLOCK) void k_stage_values(const int32_t* __restrict__ lut,
+                                                        const uint4* __restrict__ boards,
+                                                        int64_t n, int64_t* __restrict__ values,
+                                                        Params p, StageParams sp) {
+    const int64_t tid = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    const int64_t i = tid >> 3;
+    const uint32_t g = threadIdx.x & 7u;
+    const bool live = i < n;  // dead groups keep their lanes for the shuffles and the vote
+    const Board b = load_board(boards, live ? i : n - 1);
+    const uint32_t st = stage_of(b, sp);
+    const uint64_t nib = nibbles(sym(b, g));
+    uint32_t e[T];
+    int32_t v[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) e[t] = st * sp.stride + entry(p, nib, t);
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] = lut[e[t]];
+    resolve<T, false>(lut, sp, e, v, st, e, v, st);
+    int64_t s = 0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) s += v[t];
+    s = group_sum(s);
+    if (live && g == 0u) values[i] = s;
+}
+
+// The table pointer of the policy kernel: read-only for act; the TD step's launch writes the
+// promoted entries, so there the const and the __restrict__ go.
+template <bool TD>
+using PolicyLut = std::conditional_t<TD, int32_t*, const int32_t* __restrict__>;
+
+template <int T, bool TD>
+__global__ __launch_bounds__(BLOCK) void k_stage_policy(
+    PolicyLut<TD> lut, const uint4* __restrict__ boards, int64_t n, int64_t* __restrict__ q_out,
+    uint8_t* __restrict__ action_out, uint4* __restrict__ after_out,
+    const uint4* __restrict__ prev, const uint8_t* __restrict__ has_prev, int32_t lr_num,
+    int32_t lr_shift, int32_t* __restrict__ delta_out, int64_t* __restrict__ err_out, Params p,
+    StageParams sp) {
+    const PolicyLane l = policy_lane<BLOCK>(boards, n);
+    const uint32_t st = stage_of(l.s, sp);  // the afterstate's stage: a merge can raise it
+    uint32_t e[T], pe[T];
+    int32_t v[T], pv[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) e[t] = st * sp.stride + entry(p, l.nib, t);
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] = l.ok ? lut[e[t]] : 0;
+    bool hp = false, mine = false;  // mine: this lane gathers (and promotes) prev's entries
+    uint32_t pst = 0, unset = 0;
+    if constexpr (TD) {
+        hp = has_prev[l.bi] != 0;
+        mine = hp && l.a == 0u;
+        const Board pb = load_board(prev, l.bi);
+        pst = stage_of(pb, sp);
+        const uint64_t pnib = nibbles(sym(pb, l.g));
+#pragma unroll
+        for (int t = 0; t < T; ++t) pe[t] = pst * sp.stride + entry(p, pnib, t);
+#pragma unroll
+        for (int t = 0; t < T; ++t) pv[t] = mine ? lut[pe[t]] : 0;
+#pragma unroll
+        for (int t = 0; t < T; ++t) unset |= pv[t] == UNSET ? 1u << t : 0u;
+        resolve<T, true>(lut, sp, e, v, st, pe, pv, pst);
+    } else {
+        resolve<T, false>(lut, sp, e, v, st, e, v, st);
+    }
+    int64_t sum = 0, psum = 0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) sum += v[t];
+    sum = group_sum(sum);
+    const Best m = best_move<8>(l.ok ? ((int64_t)l.gain << F) + sum : INT64_MIN, l.lane);
+    if constexpr (TD) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) psum += pv[t];
+        psum = group_sum(psum);  // V(prev) in the group a == 0
+    }
+    if (!l.live) return;
+    if constexpr (TD) {
+        // promotion: the value the entry resolves to, into the entries this lane found UNSET.
+        // `unset` is 0 outside the groups a == 0 of boards with has_prev.
+#pragma unroll
+        for (int t = 0; t < T; ++t)
+            if ((unset >> t) & 1u) lut[pe[t]] = pv[t];
+    }
+    if (q_out != nullptr && (l.lane & 31u) < 4u) {
+        const uint32_t k = l.lane & 3u;
+        q_out[l.i * 4 + k] = k == 0u ? m.q0 : k == 1u ? m.q1 : k == 2u ? m.q2 : m.q3;
+    }
+    if (action_out != nullptr && (l.lane & 31u) == 0u) action_out[l.i] = (uint8_t)m.act;
+    // the lane (a == action, g == 0) holds after(b, action); with no legal move after = b
+    if (after_out != nullptr && l.a == m.act && l.g == 0u) {
+        const Board o = l.legal != 0u ? l.s : l.b;
+        after_out[l.i] = make_uint4(o.r0, o.r1, o.r2, o.r3);
+    }
+    if constexpr (TD) {
+        if ((l.lane & 31u) == 0u) {
+            const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
+            delta_out[l.i] = td.delta;
+            if (err_out != nullptr) err_out[l.i] = td.err;
+        }
+    }
+}
+
+// The update's block, as in g2048_ntuple.hip: 128 boards, their adds summed per entry in an LDS
+// hash table first (the key is the staged entry index, < 2^30), then one atomic per used slot.
+// The entries it adds into were promoted by the policy launch, so none of them is UNSET and the
+// table is never read here.
+constexpr int UBLOCK = 1024, SLOT_BITS = 13;
+constexpr uint32_t SLOTS = 1u << SLOT_BITS;  // 64 KiB of LDS
+
+template <int T>
+__global__ __launch_bounds__(UBLOCK) void k_stage_update(
+    int32_t* __restrict__ lut, const uint4* __restrict__ boards, int64_t n,
+    uint4* __restrict__ prev, uint8_t* __restrict__ has_prev, const uint8_t* __restrict__ action,
+    const int32_t* __restrict__ delta, Params p, StageParams sp) {
+    __shared__ uint32_t keys[SLOTS];
+    __shared__ uint32_t sums[SLOTS];
+    clear_keys<SLOT_BITS, UBLOCK>(keys);
+    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) sums[s] = 0u;
+    __syncthreads();
+    const int64_t tid = (int64_t)blockIdx.x * UBLOCK + threadIdx.x;
+    const int64_t i = tid >> 3;
+    const uint32_t g = threadIdx.x & 7u;
+    const bool live = i < n;
+    uint32_t* table = reinterpret_cast<uint32_t*>(lut);  // additions modulo 2^32
+    const uint32_t d = live && has_prev[i] != 0 ? (uint32_t)delta[i] : 0u;
+    if (d != 0u) {
+        const Board pb = load_board(prev, i);
+        const uint32_t base = stage_of(pb, sp) * sp.stride;
+        const uint64_t nib = nibbles(sym(pb, g));
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const uint32_t e = base + entry(p, nib, t);
+            const uint32_t slot = claim_slot<SLOT_BITS>(keys, e);
+            if (slot != NO_SLOT) atomicAdd(&sums[slot], d);
+            else atomicAdd(&table[e], d);
+        }
+    }
+    // every read of prev[i] and has_prev[i] lies before this barrier, lane 0's stores after it
+    __syncthreads();
+    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
+        const uint32_t k = keys[s], v = sums[s];
+        if (k != NO_KEY && v != 0u) atomicAdd(&table[k], v);
+    }
+    if (live && g == 0u) commit_prev(boards, i, action, prev, has_prev);
+}
+
+thread_local std::string g_err;
+
+int check_stages(const char* who, const g2048_ntstage_spec* stages) {
+    if (stages == nullptr) return refuse(g_err, "%s: stages is NULL", who);
+    const int S = stages->n_stages;
+    if (S < 1 || S > MAXS) return refuse(g_err, "%s: n_stages = %d outside [1, %d]", who, S, MAXS);
+    for (int k = 0; k < MAXS - 1; ++k) {
+        const int b = stages->bounds[k];
+        if (k >= S - 1) {
+            if (b != 0)
+                return refuse(g_err, "%s: unused bound %d = %d must be 0 (n_stages = %d)", who, k,
+                              b, S);
+            continue;
+        }
+        if (b < 1 || b > G2048_NTSTAGE_MAX_BOUND)
+            return refuse(g_err, "%s: bound %d = %d outside [1, %d]", who, k, b,
+                          G2048_NTSTAGE_MAX_BOUND);
+        if (k > 0 && b <= stages->bounds[k - 1])
+            return refuse(g_err, "%s: bounds must be strictly increasing (bound %d = %d after %d)",
+                          who, k, b, stages->bounds[k - 1]);
+    }
+    return G2048_OK;
+}
+
+// the spec, the stage spec and the rest of check_common
+int check_staged(const char* who, const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
+                 const int32_t* lut, const uint8_t* boards, int64_t n) {
+    int rc = check_spec(g_err, who, spec);
+    if (rc != G2048_OK) return rc;
+    rc = check_stages(who, stages);
+    if (rc != G2048_OK) return rc;
+    return check_common(g_err, who, spec, lut, boards, n);
+}
+
+StageParams make_stage_params(const g2048_ntuple_spec& spec, const g2048_ntstage_spec& stages) {
+    StageParams sp = {};
+    sp.stride = (uint32_t)spec.n_tuples << (4 * spec.n_cells);
+    sp.n_stages = (uint32_t)stages.n_stages;
+    for (int k = 0; k < MAXS; ++k)
+        sp.bounds |= (uint64_t)(k < stages.n_stages - 1 ? stages.bounds[k] : 255u) << (8 * k);
+    return sp;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* g2048_ntstage_last_error(void) { return g_err.c_str(); }
+
+int64_t g2048_ntstage_lut_entries(const g2048_ntuple_spec* spec,
+                                  const g2048_ntstage_spec* stages) {
+    const char* who = "ntstage_lut_entries";
+    int rc = check_spec(g_err, who, spec);
+    if (rc != G2048_OK) return rc;
+    rc = check_stages(who, stages);
+    if (rc != G2048_OK) return rc;
+    return (int64_t)stages->n_stages * ((int64_t)spec->n_tuples << (4 * spec->n_cells));
+}
+
+int g2048_ntstage_values(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
+                         const int32_t* lut_dev, const uint8_t* boards_dev, int64_t n,
+                         int64_t* values_out_dev, int device_id, void* stream) {
+    const int rc = check_staged("ntstage_values", spec, stages, lut_dev, boards_dev, n);
+    if (rc != G2048_OK) return rc;
+    if (values_out_dev == nullptr)
+        return refuse(g_err, "ntstage_values: values_out_dev is NULL");
+    if (((uintptr_t)values_out_dev & 7u) != 0)
+        return refuse(g_err, "ntstage_values: values_out_dev must be 8-byte aligned");
+    const Params p = make_params(*spec);
+    const StageParams sp = make_stage_params(*spec, *stages);
+    DeviceGuard guard(device_id);
+    hipStream_t st = (hipStream_t)stream;
+    const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
+    DISPATCH_T(spec->n_tuples,
+               (k_stage_values<TT><<<grid_for(n, BLOCK / 8), dim3(BLOCK), 0, st>>>(
+                   lut_dev, boards, n, values_out_dev, p, sp)));
+    G_HIP(hipGetLastError());
+    return G2048_OK;
+}
+
+int g2048_ntstage_act(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
+                      const int32_t* lut_dev, const uint8_t* boards_dev, int64_t n,
+                      int64_t* q_out_dev, uint8_t* action_out_dev, uint8_t* after_out_dev,
+                      int device_id, void* stream) {
+    const int rc = check_staged("ntstage_act", spec, stages, lut_dev, boards_dev, n);
+    if (rc != G2048_OK) return rc;
+    if (q_out_dev == nullptr && action_out_dev == nullptr && after_out_dev == nullptr)
+        return refuse(g_err, "ntstage_act: all three outputs are NULL");
+    if (((uintptr_t)q_out_dev & 7u) != 0)
+        return refuse(g_err, "ntstage_act: q_out_dev must be 8-byte aligned");
+    if (((uintptr_t)after_out_dev & 15u) != 0)
+        return refuse(g_err, "ntstage_act: after_out_dev must be 16-byte aligned");
+    const Params p = make_params(*spec);
+    const StageParams sp = make_stage_params(*spec, *stages);
+    DeviceGuard guard(device_id);
+    hipStream_t st = (hipStream_t)stream;
+    const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
+    uint4* after = reinterpret_cast<uint4*>(after_out_dev);
+    DISPATCH_T(spec->n_tuples,
+               (k_stage_policy<TT, false><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
+                   lut_dev, boards, n, q_out_dev, action_out_dev, after, nullptr, nullptr, 0, 0,
+                   nullptr, nullptr, p, sp)));
+    G_HIP(hipGetLastError());
+    return G2048_OK;
+}
+
+int g2048_ntstage_td_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
+                          int32_t* lut_dev, const uint8_t* boards_dev, int64_t n,
+                          uint8_t* prev_dev, uint8_t* has_prev_dev, int32_t lr_num,
+                          int32_t lr_shift, uint8_t* action_out_dev, int32_t* delta_out_dev,
+                          int64_t* err_out_dev, int device_id, void* stream) {
+    const char* who = "ntstage_td_step";
+    int rc = check_staged(who, spec, stages, lut_dev, boards_dev, n);
+    if (rc != G2048_OK) return rc;
+    rc = check_td_args(g_err, who, prev_dev, has_prev_dev, lr_num, lr_shift, action_out_dev,
+                       delta_out_dev, err_out_dev);
+    if (rc != G2048_OK) return rc;
+    const Params p = make_params(*spec);
+    const StageParams sp = make_stage_params(*spec, *stages);
+    DeviceGuard guard(device_id);
+    hipStream_t st = (hipStream_t)stream;
+    const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
+    uint4* prev = reinterpret_cast<uint4*>(prev_dev);
+    DISPATCH_T(spec->n_tuples,
+               (k_stage_policy<TT, true><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
+                   lut_dev, boards, n, nullptr, action_out_dev, nullptr, prev, has_prev_dev,
+                   lr_num, lr_shift, delta_out_dev, err_out_dev, p, sp)));
+    G_HIP(hipGetLastError());
+    DISPATCH_T(spec->n_tuples,
+               (k_stage_update<TT><<<grid_for(n, UBLOCK / 8), dim3(UBLOCK), 0, st>>>(
+                   lut_dev, boards, n, prev, has_prev_dev, action_out_dev, delta_out_dev, p, sp)));
+    G_HIP(hipGetLastError());
+    return G2048_OK;
+}
+
+}  // extern "C"

@@ -13,6 +13,8 @@ tests/ntuple_ref.py.
   BatchedPlayer(..., ntuple=net).play("ntuple")   whole games under the greedy afterstate policy
   NTupleNetwork.search / play("ntuple_search")    expectimax with the table at the leaves
                                                   (g2048.ntsearch, a library of its own)
+  g2048.ntstage.StagedNTupleNetwork   one table per stage of the game (by largest tile): it takes
+                                      NTupleNetwork's place in NTupleTrainer and play("ntuple")
 
 The binding is this module's own (not in _native.SIGNATURES: libg2048.so's ABI stays as it is).
 There is no CPU fallback: a missing library or a non-GPU tensor raises.

@@ -15,7 +15,7 @@
 //   k_stage_update  8 boards per wave, 128 per block: lane g adds delta into its T entries of
 //                   idx(prev, g, .) at stage(prev) through the block's LDS merge table.
 // What is new:
-//   M(b) and the stage  M(b) is taken on the un-transformed board in registers: the even and the
+//   M(b) and the stage  (g2048_ntstage_dev.hpp, shared with g2048_stagesearch.hip)  M(b) is taken on the un-transformed board in registers: the even and the
 //       odd bytes of the four words as 16-bit pairs, seven v_pk_max_u16 and one max of the two
 //       halves.  The bounds ride in the params struct as eight bytes (255 past S - 1, above any
 //       exponent), wave-uniform, so the stage is seven compares against scalar operands.  The
@@ -41,6 +41,7 @@
 #include "../../include/g2048_ntuple.h"
 #include "g2048_board.hpp"
 #include "g2048_ntuple_dev.hpp"
+#include "g2048_ntstage_dev.hpp"
 
 namespace {
 
@@ -48,43 +49,6 @@ using namespace g2048;
 using namespace g2048::nt;
 
 constexpr int BLOCK = 256;
-constexpr int MAXS = G2048_NTSTAGE_MAX_STAGES;
-constexpr int32_t UNSET = G2048_NTSTAGE_UNSET;
-
-struct StageParams {
-    uint32_t stride;    // T * 16^m, the entries of one stage
-    uint32_t n_stages;  // S
-    uint64_t bounds;    // byte k = bounds[k] for k < S - 1, 255 (above any exponent) past that
-};
-
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u16x2 pairs(uint32_t w) { return __builtin_bit_cast(u16x2, w); }
-
-// M(b): the largest exponent byte.  Even and odd bytes as 16-bit pairs, a packed max over the
-// eight words, then the larger half.
-__device__ __forceinline__ uint32_t max_tile(const Board& b) {
-    constexpr uint32_t EVEN = 0x00FF00FFu;
-    u16x2 m = __builtin_elementwise_max(pairs(b.r0 & EVEN), pairs((b.r0 >> 8) & EVEN));
-    m = __builtin_elementwise_max(m, pairs(b.r1 & EVEN));
-    m = __builtin_elementwise_max(m, pairs((b.r1 >> 8) & EVEN));
-    m = __builtin_elementwise_max(m, pairs(b.r2 & EVEN));
-    m = __builtin_elementwise_max(m, pairs((b.r2 >> 8) & EVEN));
-    m = __builtin_elementwise_max(m, pairs(b.r3 & EVEN));
-    m = __builtin_elementwise_max(m, pairs((b.r3 >> 8) & EVEN));
-    const uint32_t w = __builtin_bit_cast(uint32_t, m);
-    return max(w & 0xFFFFu, w >> 16);
-}
-
-// stage(b): the number of bounds that M(b) reaches
-__device__ __forceinline__ uint32_t stage_of(const Board& b, const StageParams& sp) {
-    const uint32_t m = max_tile(b);
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < MAXS - 1; ++k) s += m >= ((uint32_t)(sp.bounds >> (8 * k)) & 0xFFu) ? 1u : 0u;
-    return s;
-}
-
 // The fall-through: v[t] holds lut[e[t]] of a lane at stage s (0 in a lane that gathers
 // nothing).  Round r reads the entry r stages down for every value still UNSET in a lane with
 // s >= r; what is UNSET at stage 0 is 0.  With TWO a second set (pe, pv, ps) shares the rounds.
@@ -268,45 +232,14 @@ __global__ __launch_bounds__(UBLOCK) void k_stage_update(
 
 thread_local std::string g_err;
 
-int check_stages(const char* who, const g2048_ntstage_spec* stages) {
-    if (stages == nullptr) return refuse(g_err, "%s: stages is NULL", who);
-    const int S = stages->n_stages;
-    if (S < 1 || S > MAXS) return refuse(g_err, "%s: n_stages = %d outside [1, %d]", who, S, MAXS);
-    for (int k = 0; k < MAXS - 1; ++k) {
-        const int b = stages->bounds[k];
-        if (k >= S - 1) {
-            if (b != 0)
-                return refuse(g_err, "%s: unused bound %d = %d must be 0 (n_stages = %d)", who, k,
-                              b, S);
-            continue;
-        }
-        if (b < 1 || b > G2048_NTSTAGE_MAX_BOUND)
-            return refuse(g_err, "%s: bound %d = %d outside [1, %d]", who, k, b,
-                          G2048_NTSTAGE_MAX_BOUND);
-        if (k > 0 && b <= stages->bounds[k - 1])
-            return refuse(g_err, "%s: bounds must be strictly increasing (bound %d = %d after %d)",
-                          who, k, b, stages->bounds[k - 1]);
-    }
-    return G2048_OK;
-}
-
 // the spec, the stage spec and the rest of check_common
 int check_staged(const char* who, const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
                  const int32_t* lut, const uint8_t* boards, int64_t n) {
     int rc = check_spec(g_err, who, spec);
     if (rc != G2048_OK) return rc;
-    rc = check_stages(who, stages);
+    rc = check_stages(g_err, who, stages);
     if (rc != G2048_OK) return rc;
     return check_common(g_err, who, spec, lut, boards, n);
-}
-
-StageParams make_stage_params(const g2048_ntuple_spec& spec, const g2048_ntstage_spec& stages) {
-    StageParams sp = {};
-    sp.stride = (uint32_t)spec.n_tuples << (4 * spec.n_cells);
-    sp.n_stages = (uint32_t)stages.n_stages;
-    for (int k = 0; k < MAXS; ++k)
-        sp.bounds |= (uint64_t)(k < stages.n_stages - 1 ? stages.bounds[k] : 255u) << (8 * k);
-    return sp;
 }
 
 }  // namespace
@@ -320,7 +253,7 @@ int64_t g2048_ntstage_lut_entries(const g2048_ntuple_spec* spec,
     const char* who = "ntstage_lut_entries";
     int rc = check_spec(g_err, who, spec);
     if (rc != G2048_OK) return rc;
-    rc = check_stages(who, stages);
+    rc = check_stages(g_err, who, stages);
     if (rc != G2048_OK) return rc;
     return (int64_t)stages->n_stages * ((int64_t)spec->n_tuples << (4 * spec->n_cells));
 }

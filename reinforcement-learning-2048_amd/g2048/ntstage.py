@@ -13,12 +13,13 @@ in which boards are processed, and it is checked bit for bit against tests/ntsta
   StagedNTupleNetwork(spec, bounds, device)   owns `lut` int32 [S, T, 16^m], all UNSET when fresh:
                     values(), act(), td_step() with NTupleNetwork's signatures, so
                     NTupleTrainer(staged, ...) and BatchedPlayer(..., ntuple=staged).play("ntuple")
-                    work as they are; from_network(), resolved(), stage_of(), set_counts(),
-                    save() / load()
+                    work as they are; expectimax(), from_network(), resolved(), stage_of(),
+                    set_counts(), save() / load()
 
-A staged network is not an NTupleNetwork: the expectimax search (`play("ntuple_search")`,
-g2048.ntsearch), TCTrainer and TDLambdaTrainer refuse it.  `resolved(stage)` gives a plain
-NTupleNetwork of one fixed stage for them.
+A staged network is not an NTupleNetwork: the single-table expectimax search
+(`play("ntuple_search")`, g2048.ntsearch), TCTrainer and TDLambdaTrainer refuse it.
+`resolved(stage)` gives a plain NTupleNetwork of one fixed stage for them.  The search that values
+every leaf at its own stage is `expectimax()` (g2048.stagesearch, `play("ntstage_search")`).
 
 The binding is this module's own (not in _native.SIGNATURES: libg2048.so's ABI stays as it is).
 There is no CPU fallback: a missing library or a non-GPU tensor raises.
@@ -181,10 +182,22 @@ class StagedNTupleNetwork:
 
     def search(self, boards: torch.Tensor, depth: int = 2, p4: float = 0.5, values=True,
                actions=True, values_out=None, actions_out=None):
-        """Not available: the search reads one table.  `resolved(stage).search(...)` searches
-        with one fixed stage."""
-        raise TypeError("the expectimax search takes an NTupleNetwork, not a staged network; "
-                        "use resolved(stage).search(...)")
+        """Not available: g2048.ntsearch reads one table.  `expectimax(...)` is the search over
+        this network, every leaf at its own stage; `resolved(stage).search(...)` searches with
+        one fixed stage."""
+        raise TypeError("the single-table expectimax search takes an NTupleNetwork, not a staged "
+                        "network; use expectimax(...) (every leaf at its own stage) or "
+                        "resolved(stage).search(...)")
+
+    def expectimax(self, boards: torch.Tensor, depth: int = 2, p4: float = 0.5, values=True,
+                   actions=True, values_out=None, actions_out=None):
+        """Expectimax `depth` player moves deep with every leaf valued at its own stage
+        (g2048.stagesearch.expectimax): (actions u8 [n], values i64 [n, 4]).  Depth 1 is act().
+        The table is only read: nothing is promoted."""
+        from . import stagesearch
+
+        return stagesearch.expectimax(self, boards, depth, p4, values, actions, values_out,
+                                      actions_out)
 
     def td_step(self, boards, prev, has_prev, lr_num, lr_shift, actions_out, delta_out,
                 err_out=None):

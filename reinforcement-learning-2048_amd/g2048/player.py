@@ -22,6 +22,10 @@ Policies (one game per board, every board plays to its end):
            search_depth 1..3 player moves deep, the player's p4 at the chance nodes), then the env
            step.  Depth 1 is the ntuple policy.  Always a legal move; history tuples as
            play_game's.
+  ntstage_search  the same search over a multi-stage network (g2048.stagesearch,
+           ntuple=StagedNTupleNetwork, search_depth 1..3, the player's p4): every leaf is valued
+           at its own stage.  Depth 1 is the ntuple policy of that network.  Always a legal move;
+           history tuples as play_game's.
 
 Results follow the reference's bookkeeping: `moves` = steps taken (history length, terminal
 step included), `merge_score`, `max_tile`; `max_tile_frequency()` is notebook_utils'
@@ -33,7 +37,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ntsearch, qnet, search
+from . import ntsearch, ntstage, qnet, search, stagesearch
 from .env import VecEnv2048
 from .nets import Conv2048
 
@@ -183,9 +187,20 @@ class BatchedPlayer:
             if self.search_depth > ntsearch.MAX_DEPTH:
                 raise ValueError(f"the ntuple_search policy searches 1..{ntsearch.MAX_DEPTH} "
                                  f"moves deep (search_depth = {self.search_depth})")
-        if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple", "ntuple_search"):
+        if policy == "ntstage_search":
+            if self.ntuple is None:
+                raise ValueError("the ntstage_search policy needs a network "
+                                 "(ntuple=StagedNTupleNetwork)")
+            if not isinstance(self.ntuple, ntstage.StagedNTupleNetwork):
+                raise TypeError("the ntstage_search policy takes a StagedNTupleNetwork "
+                                "(ntuple_search searches an NTupleNetwork)")
+            if self.search_depth > stagesearch.MAX_DEPTH:
+                raise ValueError(f"the ntstage_search policy searches 1..{stagesearch.MAX_DEPTH} "
+                                 f"moves deep (search_depth = {self.search_depth})")
+        if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple", "ntuple_search",
+                          "ntstage_search"):
             raise ValueError("policy must be 'random', 'upleft', 'greedy', 'expectimax', "
-                             "'ntuple' or 'ntuple_search'")
+                             "'ntuple', 'ntuple_search' or 'ntstage_search'")
         env = self._env(egreedy="fixed" if policy == "random" else "compat")
         dev = self.device
         n = self.n
@@ -226,6 +241,12 @@ class BatchedPlayer:
             elif policy == "ntuple_search":
                 act, _ = ntsearch.expectimax(self.ntuple, env.board, self.search_depth, self.p4,
                                              values=False)
+                reward, done, _ = env.step(act)
+                ended = done.bool()
+                newly_stuck = None
+            elif policy == "ntstage_search":
+                act, _ = stagesearch.expectimax(self.ntuple, env.board, self.search_depth,
+                                                self.p4, values=False)
                 reward, done, _ = env.step(act)
                 ended = done.bool()
                 newly_stuck = None

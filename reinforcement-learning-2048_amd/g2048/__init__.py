@@ -5,7 +5,8 @@ src/dqn_lib.py): the env step, replay buffer and train_step, batched over tens o
 boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI include/g2048.h).
 """
 from ._native import NativeError, load as load_native  # noqa: F401
-from . import ntlambda, ntsearch, ntstage, nttc, ntuple, search, stagesearch  # noqa: F401
+from . import (ntlambda, ntrestart, ntsearch, ntstage, nttc, ntuple, search,  # noqa: F401
+               stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
                      generate_replay_buffer_using_expectimax)
@@ -14,10 +15,11 @@ from .ntuple import (TUPLES_2x4, TUPLES_4x6, NTupleNetwork, NTupleSpec,  # noqa:
 from .nttc import TCState, TCTrainer  # noqa: F401
 from .ntlambda import TDLambdaState, TDLambdaTrainer  # noqa: F401
 from .ntstage import StagedNTupleNetwork  # noqa: F401
+from .ntrestart import RestartPool  # noqa: F401
 
 __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIONS", "NativeError",
            "load_native", "search", "SearchWeights", "expectimax",
            "generate_replay_buffer_using_expectimax", "ntuple", "NTupleSpec", "NTupleNetwork",
            "NTupleTrainer", "TUPLES_4x6", "TUPLES_2x4", "ntsearch",
            "nttc", "TCState", "TCTrainer", "ntlambda", "TDLambdaState", "TDLambdaTrainer",
-           "ntstage", "StagedNTupleNetwork", "stagesearch"]
+           "ntstage", "StagedNTupleNetwork", "stagesearch", "ntrestart", "RestartPool"]

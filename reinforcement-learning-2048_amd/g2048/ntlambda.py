@@ -132,3 +132,5 @@ class TDLambdaTrainer(NT.NTupleTrainer):
             self.lam.step(self.env.board, self.lr_num, self.lr_shift, self.actions, self.delta,
                           self.err)
             self.env.step(self.actions, reward=self.reward, done=self.done, legal=self.legal)
+            if self.restart is not None:
+                self.restart.apply(self.env, self.done)

@@ -155,3 +155,5 @@ class TCTrainer(NT.NTupleTrainer):
             self.tc.tc_step(self.env.board, self.prev, self.has_prev, self.lr_num, self.lr_shift,
                             self.actions, self.delta, self.err, self.work)
             self.env.step(self.actions, reward=self.reward, done=self.done, legal=self.legal)
+            if self.restart is not None:
+                self.restart.apply(self.env, self.done)

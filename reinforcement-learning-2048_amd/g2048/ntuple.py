@@ -15,6 +15,8 @@ tests/ntuple_ref.py.
                                                   (g2048.ntsearch, a library of its own)
   g2048.ntstage.StagedNTupleNetwork   one table per stage of the game (by largest tile): it takes
                                       NTupleNetwork's place in NTupleTrainer and play("ntuple")
+  g2048.ntrestart.RestartPool   per-board snapshots by largest tile; NTupleTrainer(...,
+                                restart=pool) restarts some episodes from them (a carousel)
 
 The binding is this module's own (not in _native.SIGNATURES: libg2048.so's ABI stays as it is).
 There is no CPU fallback: a missing library or a non-GPU tensor raises.
@@ -272,10 +274,12 @@ class NTupleTrainer:
     """Afterstate TD(0) self-play: n_boards auto-resetting boards, every step the greedy move of
     the current table, the table moved toward reward + V(next afterstate).  `step(k)` enqueues
     k x (td_step, env.step) on the current stream with no host sync; `episodes()` reads the
-    finished episodes from the env's device log."""
+    finished episodes from the env's device log.  With `restart` (a g2048.ntrestart.RestartPool
+    of n_boards boards on the network's device) every iteration ends with `restart.apply`, one
+    more launch; this class and its subclasses share the keyword."""
 
     def __init__(self, net: NTupleNetwork, n_boards: int, seed: int = 0x2048, p4: float = 0.5,
-                 lr_num: int = 1, lr_shift: int | None = None, log_slots: int = 8):
+                 lr_num: int = 1, lr_shift: int | None = None, log_slots: int = 8, restart=None):
         self.net = net
         self.n = int(n_boards)
         self.lr_num = int(lr_num)
@@ -285,6 +289,14 @@ class NTupleTrainer:
                              f"[0, {MAX_LR_SHIFT}]")
         from .env import VecEnv2048
 
+        if restart is not None:
+            from .ntrestart import RestartPool
+
+            if not isinstance(restart, RestartPool):
+                raise TypeError("restart must be a RestartPool or None")
+            if restart.n != self.n or restart.device != net.device:
+                raise ValueError(f"restart must hold {self.n} boards on {net.device}")
+        self.restart = restart
         dev = net._gpu()
         self.env = VecEnv2048(self.n, seed=seed, device=dev, p4=p4)
         self.log = self.env.attach_episode_log(log_slots)
@@ -303,6 +315,8 @@ class NTupleTrainer:
             self.net.td_step(self.env.board, self.prev, self.has_prev, self.lr_num, self.lr_shift,
                              self.actions, self.delta, self.err)
             self.env.step(self.actions, reward=self.reward, done=self.done, legal=self.legal)
+            if self.restart is not None:
+                self.restart.apply(self.env, self.done)
 
     def episodes(self, strict: bool = True) -> dict:
         """Records of the episodes finished since the last call (EpisodeLog.read; host sync)."""

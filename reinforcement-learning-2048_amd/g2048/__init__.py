@@ -6,7 +6,7 @@ boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI 
 """
 from ._native import NativeError, load as load_native  # noqa: F401
 from . import (ntlambda, ntmean, ntrestart, ntsearch, ntstage, nttc, ntuple,  # noqa: F401
-               search, stagesearch)
+               search, stagemean, stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
                      generate_replay_buffer_using_expectimax)
@@ -17,6 +17,7 @@ from .ntlambda import TDLambdaState, TDLambdaTrainer  # noqa: F401
 from .ntstage import StagedNTupleNetwork  # noqa: F401
 from .ntrestart import RestartPool  # noqa: F401
 from .ntmean import MeanState, MeanTrainer, default_mean_lr_shift  # noqa: F401
+from .stagemean import StagedMeanState, StagedMeanTrainer  # noqa: F401
 
 __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIONS", "NativeError",
            "load_native", "search", "SearchWeights", "expectimax",
@@ -24,4 +25,5 @@ __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIO
            "NTupleTrainer", "TUPLES_4x6", "TUPLES_2x4", "ntsearch",
            "nttc", "TCState", "TCTrainer", "ntlambda", "TDLambdaState", "TDLambdaTrainer",
            "ntstage", "StagedNTupleNetwork", "stagesearch", "ntrestart", "RestartPool",
-           "ntmean", "MeanState", "MeanTrainer", "default_mean_lr_shift"]
+           "ntmean", "MeanState", "MeanTrainer", "default_mean_lr_shift",
+           "stagemean", "StagedMeanState", "StagedMeanTrainer"]

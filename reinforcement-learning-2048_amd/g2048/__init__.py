@@ -5,8 +5,8 @@ src/dqn_lib.py): the env step, replay buffer and train_step, batched over tens o
 boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI include/g2048.h).
 """
 from ._native import NativeError, load as load_native  # noqa: F401
-from . import (ntlambda, ntmean, ntrestart, ntsearch, ntstage, nttc, ntuple,  # noqa: F401
-               search, stagemean, stagesearch)
+from . import (ntlambda, ntmean, ntmeantc, ntrestart, ntsearch, ntstage, nttc,  # noqa: F401
+               ntuple, search, stagemean, stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
                      generate_replay_buffer_using_expectimax)
@@ -18,6 +18,7 @@ from .ntstage import StagedNTupleNetwork  # noqa: F401
 from .ntrestart import RestartPool  # noqa: F401
 from .ntmean import MeanState, MeanTrainer, default_mean_lr_shift  # noqa: F401
 from .stagemean import StagedMeanState, StagedMeanTrainer  # noqa: F401
+from .ntmeantc import MeanTCState, MeanTCTrainer, default_meantc_lr_shift  # noqa: F401
 
 __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIONS", "NativeError",
            "load_native", "search", "SearchWeights", "expectimax",
@@ -26,4 +27,5 @@ __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIO
            "nttc", "TCState", "TCTrainer", "ntlambda", "TDLambdaState", "TDLambdaTrainer",
            "ntstage", "StagedNTupleNetwork", "stagesearch", "ntrestart", "RestartPool",
            "ntmean", "MeanState", "MeanTrainer", "default_mean_lr_shift",
-           "stagemean", "StagedMeanState", "StagedMeanTrainer"]
+           "stagemean", "StagedMeanState", "StagedMeanTrainer",
+           "ntmeantc", "MeanTCState", "MeanTCTrainer", "default_meantc_lr_shift"]

@@ -34,7 +34,7 @@
 #include "g2048_ntuple_dev.hpp"
 
 // G2048_NTLAMBDA_SLOT_BITS, if defined, fixes log2 of the LDS merge table's slots for every T
-// (slot_bits)
+// (lam_slot_bits)
 
 // -DG2048_NTLAMBDA_COUNT_BYPASS: a measuring build (tools/ntlambda_bench.py --lib) that counts the
 // update's adds and those of them that found no slot, and exports g2048_ntlambda_debug_counts.
@@ -107,7 +107,7 @@ constexpr int UBLOCK = 1024;
 // 6144 keys at H = 3 fit either, the two take the same time with adds and the larger one 5 us
 // more without, so T <= 2 keeps TD(0)'s size.
 template <int T>
-constexpr int slot_bits() {
+constexpr int lam_slot_bits() {
 #ifdef G2048_NTLAMBDA_SLOT_BITS
     return G2048_NTLAMBDA_SLOT_BITS;
 #else
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(UBLOCK) void k_lam_update(
     uint4* __restrict__ hist, uint8_t* __restrict__ head, uint8_t* __restrict__ depth, uint32_t H,
     uint32_t lam_shift, const uint8_t* __restrict__ action, const int32_t* __restrict__ delta,
     Params p) {
-    constexpr int SLOT_BITS = slot_bits<T>();
+    constexpr int SLOT_BITS = lam_slot_bits<T>();
     constexpr uint32_t SLOTS = 1u << SLOT_BITS;
     static_assert(SLOTS * 8u <= 160u * 1024u, "the LDS table must fit a CU's 160 KiB");
     __shared__ uint32_t keys[SLOTS];

@@ -3,29 +3,12 @@
 //
 // The rule is defined in include/g2048_ntmean.h; every value is an integer and the result is
 // checked bit for bit against tests/ntmean_ref.py.  No float anywhere.  The library takes the spec
-// and the table of g2048_ntuple.h and does not link against another library of the project.  What
-// it has in common with g2048_ntuple.hip is g2048_ntuple_dev.hpp's: the index helpers, the
-// policy's lane decode, group sum, argmax and err / delta, the merge table's keys and the prev
-// commit, and the host plumbing and argument checks.  Here are the (D, C) gather, the exchange
-// that picks an entry's one owner, the floor division and the entry points.
+// and the table of g2048_ntuple.h and does not link against another library of the project.
 //
-// A step is three launches, because an entry moves by floor(D / C) over ALL hits of the step and
-// nothing orders an add in one block against a read in another:
-//   k_mean_policy  g2048_ntuple.hip's k_policy layout: 2 boards per wave, lane 32s + 8a + g
-//                  evaluates after(board s, a) under symmetry g; the groups a == 0 also gather
-//                  V(prev).  Writes action, err and delta; only reads lut.
-//   k_mean_gather  8 boards per wave, 128 per block: lane g re-forms its T entries of
-//                  idx(prev, g, .) and adds (delta, 1) into acc.  Per block the two sums of an
-//                  entry are first merged in an LDS hash table and each used slot is flushed with
-//                  two 64-bit atomic adds.
-//   k_mean_apply   the same frame: every hit re-forms its entry, the LDS key table reduces a
-//                  block's hits to one lane per distinct entry, and that lane exchanges C with 0.
-//                  The one lane of the grid that gets a non-zero C back owns the entry: it
-//                  exchanges D with 0 too and adds floor(D / C) into lut.  Lane 0 of a board's
-//                  group then commits prev / has_prev.
-// The first launch never writes lut or acc, the second touches acc only, the third never reads
-// lut.  Everything in acc moves by device-scope atomics (adds, then exchanges), so no plain load
-// ever has to see another block's atomic.
+// It composes g2048_ntuple_dev.hpp's flat policy launch (k_policy<T, true>) with
+// g2048_ntmean_dev.hpp's gather and apply over FlatIndex and MeanTail: the owner of an entry adds
+// floor(D / C) into lut.  The step's three launches and why they need no further ordering are
+// argued in g2048_ntmean_dev.hpp.  Here are the entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,168 +17,12 @@
 #include "../../include/g2048_ntmean.h"
 #include "g2048_board.hpp"
 #include "g2048_ntuple_dev.hpp"
-
-// G2048_NTMEAN_SLOT_BITS, if defined, fixes log2 of the gather's LDS slots for every T (slot_bits)
+#include "g2048_ntmean_dev.hpp"
 
 namespace {
 
 using namespace g2048;
 using namespace g2048::nt;
-
-using u64 = unsigned long long;
-
-constexpr int BLOCK = 256;
-
-template <int T>
-__global__ __launch_bounds__(BLOCK) void k_mean_policy(
-    const int32_t* __restrict__ lut, const uint4* __restrict__ boards, int64_t n,
-    uint8_t* __restrict__ action_out, const uint4* __restrict__ prev,
-    const uint8_t* __restrict__ has_prev, int32_t lr_num, int32_t lr_shift,
-    int32_t* __restrict__ delta_out, int64_t* __restrict__ err_out, Params p) {
-    const PolicyLane l = policy_lane<BLOCK>(boards, n);
-    int32_t v[T], pv[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) v[t] = l.ok ? lut[entry(p, l.nib, t)] : 0;
-    const bool hp = has_prev[l.bi] != 0;
-    const uint64_t pnib = nibbles(sym(load_board(prev, l.bi), l.g));
-#pragma unroll
-    for (int t = 0; t < T; ++t) pv[t] = (hp && l.a == 0u) ? lut[entry(p, pnib, t)] : 0;
-    int64_t sum = 0, psum = 0;
-#pragma unroll
-    for (int t = 0; t < T; ++t) sum += v[t];
-    sum = group_sum(sum);
-    const Best m = best_move<8>(l.ok ? ((int64_t)l.gain << F) + sum : INT64_MIN, l.lane);
-#pragma unroll
-    for (int t = 0; t < T; ++t) psum += pv[t];
-    psum = group_sum(psum);  // V(prev) in the group a == 0
-    if (!l.live) return;
-    if ((l.lane & 31u) == 0u) {
-        const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
-        action_out[l.i] = (uint8_t)m.act;
-        delta_out[l.i] = td.delta;
-        if (err_out != nullptr) err_out[l.i] = td.err;
-    }
-}
-
-// The gather's and the apply's block: 128 boards, lane g of a board's group of 8.
-constexpr int UBLOCK = 1024;
-
-// log2 of the gather table's slots; a slot is 16 bytes (key, D sum, C sum: a block makes at most
-// 1024 T hits, so its C fits 32 bits) and a block makes 1024 T hits.  Measured.
-template <int T>
-constexpr int slot_bits() {
-#ifdef G2048_NTMEAN_SLOT_BITS
-    return G2048_NTMEAN_SLOT_BITS;
-#else
-    return T <= 1 ? 9 : T == 2 ? 10 : 12;
-#endif
-}
-
-// the apply's table holds keys only (4 bytes a slot): room for every hit of a block at T <= 4
-constexpr int APPLY_SLOT_BITS = 13;
-
-// (D, C) of one entry into acc, straight to memory
-__device__ __forceinline__ void add_entry(u64* acc, uint32_t e, u64 d, u64 c) {
-    if (d != 0ull) atomicAdd(&acc[2u * (size_t)e], d);
-    atomicAdd(&acc[2u * (size_t)e + 1u], c);
-}
-
-template <int T>
-__global__ __launch_bounds__(UBLOCK) void k_mean_gather(
-    int64_t* __restrict__ acc_, int64_t n, const uint4* __restrict__ prev,
-    const uint8_t* __restrict__ has_prev, const int32_t* __restrict__ delta, Params p) {
-    constexpr int SLOT_BITS = slot_bits<T>();
-    constexpr uint32_t SLOTS = 1u << SLOT_BITS;
-    static_assert(SLOTS * 16u <= 160u * 1024u, "the LDS table must fit a CU's 160 KiB");
-    __shared__ uint32_t keys[SLOTS];
-    __shared__ uint32_t csum[SLOTS];
-    __shared__ u64 dsum[SLOTS];
-    clear_keys<SLOT_BITS, UBLOCK>(keys);
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
-        csum[s] = 0u;
-        dsum[s] = 0ull;
-    }
-    __syncthreads();
-    const int64_t tid = (int64_t)blockIdx.x * UBLOCK + threadIdx.x;
-    const int64_t i = tid >> 3;
-    const uint32_t g = threadIdx.x & 7u;
-    u64* acc = reinterpret_cast<u64*>(acc_);  // additions modulo 2^64
-    const int32_t d = i < n && has_prev[i] != 0 ? delta[i] : 0;
-    if (d != 0) {
-        const uint64_t nib = nibbles(sym(load_board(prev, i), g));
-        const u64 de = (u64)(int64_t)d;
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const uint32_t e = entry(p, nib, t);
-            const uint32_t slot = claim_slot<SLOT_BITS>(keys, e);
-            if (slot != NO_SLOT) {
-                atomicAdd(&dsum[slot], de);
-                atomicAdd(&csum[slot], 1u);
-            } else {
-                add_entry(acc, e, de, 1ull);
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
-        const uint32_t k = keys[s];
-        if (k != NO_KEY) add_entry(acc, k, dsum[s], (u64)csum[s]);
-    }
-}
-
-// floor(D / C) modulo 2^32, 1 <= C <= 8 n < 2^35: the truncating quotient, one lower where the
-// remainder is negative
-__device__ __forceinline__ uint32_t floor_div(int64_t D, int64_t c) {
-    int64_t q = D / c;
-    if (D - q * c < 0) --q;
-    return (uint32_t)q;
-}
-
-// Several lanes of the grid ask for one entry (one per block that hit it, and every hit that
-// found no slot).  The lane that takes the non-zero C out owns the entry.
-__device__ __forceinline__ void apply_entry(uint32_t* table, u64* acc, uint32_t e) {
-    const u64 c = atomicExch(&acc[2u * (size_t)e + 1u], 0ull);
-    if (c == 0ull) return;
-    const int64_t D = (int64_t)atomicExch(&acc[2u * (size_t)e], 0ull);
-    const uint32_t q = c == 1ull ? (uint32_t)D : floor_div(D, (int64_t)c);
-    if (q != 0u) atomicAdd(&table[e], q);
-}
-
-template <int T>
-__global__ __launch_bounds__(UBLOCK) void k_mean_apply(
-    int32_t* __restrict__ lut, int64_t* __restrict__ acc_, const uint4* __restrict__ boards,
-    int64_t n, uint4* __restrict__ prev, uint8_t* __restrict__ has_prev,
-    const uint8_t* __restrict__ action, const int32_t* __restrict__ delta, Params p) {
-    constexpr uint32_t SLOTS = 1u << APPLY_SLOT_BITS;
-    __shared__ uint32_t keys[SLOTS];
-    clear_keys<APPLY_SLOT_BITS, UBLOCK>(keys);
-    __syncthreads();
-    const int64_t tid = (int64_t)blockIdx.x * UBLOCK + threadIdx.x;
-    const int64_t i = tid >> 3;
-    const uint32_t g = threadIdx.x & 7u;
-    const bool live = i < n;
-    uint32_t* table = reinterpret_cast<uint32_t*>(lut);  // additions modulo 2^32
-    u64* acc = reinterpret_cast<u64*>(acc_);
-    const int32_t d = live && has_prev[i] != 0 ? delta[i] : 0;
-    if (d != 0) {
-        const uint64_t nib = nibbles(sym(load_board(prev, i), g));
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const uint32_t e = entry(p, nib, t);
-            // a hit that finds no slot asks for the entry itself
-            if (claim_slot<APPLY_SLOT_BITS>(keys, e) == NO_SLOT) apply_entry(table, acc, e);
-        }
-    }
-    // every read of prev[i] and has_prev[i] lies before this barrier, lane 0's stores after it
-    __syncthreads();
-    // One slot after the other.  Tried: a lane's eight exchanges of C in flight together, then
-    // its exchanges of D -- equal at 65 536 boards, slower at 4 096.
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
-        const uint32_t k = keys[s];
-        if (k != NO_KEY) apply_entry(table, acc, k);
-    }
-    if (live && g == 0u) commit_prev(boards, i, action, prev, has_prev);
-}
 
 thread_local std::string g_err;
 
@@ -208,7 +35,7 @@ const char* g2048_ntmean_last_error(void) { return g_err.c_str(); }
 int64_t g2048_ntmean_acc_bytes(const g2048_ntuple_spec* spec) {
     const int rc = nt::check_spec(g_err, "ntmean_acc_bytes", spec);
     if (rc != G2048_OK) return rc;
-    return ((int64_t)spec->n_tuples << (4 * spec->n_cells)) * 2 * (int64_t)sizeof(int64_t);
+    return table_bytes(*spec);
 }
 
 int g2048_ntmean_step(const g2048_ntuple_spec* spec, int32_t* lut_dev, int64_t* acc_dev,
@@ -219,31 +46,14 @@ int g2048_ntmean_step(const g2048_ntuple_spec* spec, int32_t* lut_dev, int64_t* 
     const char* who = "ntmean_step";
     int rc = check_common(g_err, who, spec, lut_dev, boards_dev, n);
     if (rc != G2048_OK) return rc;
-    if (acc_dev == nullptr) return refuse(g_err, "ntmean_step: acc_dev is NULL");
-    if (((uintptr_t)acc_dev & 15u) != 0)
-        return refuse(g_err, "ntmean_step: acc_dev must be 16-byte aligned");
+    rc = check_acc(g_err, who, acc_dev);
+    if (rc != G2048_OK) return rc;
     rc = check_td_args(g_err, who, prev_dev, has_prev_dev, lr_num, lr_shift, action_out_dev,
                        delta_out_dev, err_out_dev);
     if (rc != G2048_OK) return rc;
-    const Params p = make_params(*spec);
-    DeviceGuard guard(device_id);
-    hipStream_t st = (hipStream_t)stream;
-    const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
-    uint4* prev = reinterpret_cast<uint4*>(prev_dev);
-    DISPATCH_T(spec->n_tuples,
-               (k_mean_policy<TT><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
-                   lut_dev, boards, n, action_out_dev, prev, has_prev_dev, lr_num, lr_shift,
-                   delta_out_dev, err_out_dev, p)));
-    G_HIP(hipGetLastError());
-    DISPATCH_T(spec->n_tuples,
-               (k_mean_gather<TT><<<grid_for(n, UBLOCK / 8), dim3(UBLOCK), 0, st>>>(
-                   acc_dev, n, prev, has_prev_dev, delta_out_dev, p)));
-    G_HIP(hipGetLastError());
-    DISPATCH_T(spec->n_tuples, (k_mean_apply<TT><<<grid_for(n, UBLOCK / 8), dim3(UBLOCK), 0, st>>>(
-                                   lut_dev, acc_dev, boards, n, prev, has_prev_dev, action_out_dev,
-                                   delta_out_dev, p)));
-    G_HIP(hipGetLastError());
-    return G2048_OK;
+    return mean_step<MeanTail>(g_err, *spec, FlatIndex{}, lut_dev, acc_dev, boards_dev, n,
+                               prev_dev, has_prev_dev, lr_num, lr_shift, action_out_dev,
+                               delta_out_dev, err_out_dev, device_id, stream);
 }
 
 }  // extern "C"

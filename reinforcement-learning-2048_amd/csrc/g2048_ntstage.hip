@@ -14,8 +14,11 @@
 //                   V(prev) in the same burst and store the promoted values.
 //   k_stage_update  8 boards per wave, 128 per block: lane g adds delta into its T entries of
 //                   idx(prev, g, .) at stage(prev) through the block's LDS merge table.
-// What is new:
-//   M(b) and the stage  (g2048_ntstage_dev.hpp, shared with g2048_stagesearch.hip)  M(b) is taken on the un-transformed board in registers: the even and the
+// g2048_ntstage_dev.hpp holds what this file shares with the other libraries that read a staged
+// table: M(b) and the stage, the fall-through (resolve), k_stage_policy itself (the staged
+// batch-mean steps launch it too) with the argument why its promotion needs no ordering, and the
+// validation of a stage spec.  Here are k_stage_values, k_stage_update and the entry points.
+//   M(b) and the stage  M(b) is taken on the un-transformed board in registers: the even and the
 //       odd bytes of the four words as 16-bit pairs, seven v_pk_max_u16 and one max of the two
 //       halves.  The bounds ride in the params struct as eight bytes (255 past S - 1, above any
 //       exponent), wave-uniform, so the stage is seven compares against scalar operands.  The
@@ -25,17 +28,12 @@
 //       only the lanes that need it; a wave leaves the loop as soon as none of its lanes does.
 //       In the TD step the afterstate's and prev's entries share the rounds.
 //   Promotion  The groups a == 0 of the policy launch have resolved prev's entries; they store
-//       the resolved value into those they found UNSET.  Every word that launch writes is an
-//       UNSET entry, and what is written is the value the entry resolves to in the pre-call
-//       table, so any other lane that reads it, before or after the store, resolves to the same
-//       number, and two lanes that promote one entry store the same number.  Nothing has to be
-//       ordered inside the launch.  The update launch then only adds, into entries that are no
-//       longer UNSET, and never reads the table.
+//       the resolved value into those they found UNSET.  The update launch then only adds, into
+//       entries that are no longer UNSET, and never reads the table.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <string>
-#include <type_traits>
 
 #include "../../include/g2048_ntstage.h"
 #include "../../include/g2048_ntuple.h"
@@ -49,41 +47,6 @@ using namespace g2048;
 using namespace g2048::nt;
 
 constexpr int BLOCK = 256;
-// The fall-through: v[t] holds lut[e[t]] of a lane at stage s (0 in a lane that gathers
-// nothing).  Round r reads the entry r stages down for every value still UNSET in a lane with
-// s >= r; what is UNSET at stage 0 is 0.  With TWO a second set (pe, pv, ps) shares the rounds.
-// Called by whole waves: the loop's exit is a wave vote.
-template <int T, bool TWO, typename LUT>
-__device__ __forceinline__ void resolve(LUT lut, const StageParams& sp, const uint32_t (&e)[T],
-                                        int32_t (&v)[T], uint32_t s, const uint32_t (&pe)[T],
-                                        int32_t (&pv)[T], uint32_t ps) {
-    for (uint32_t r = 1; r < sp.n_stages; ++r) {
-        bool need = false;
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            need |= v[t] == UNSET && s >= r;
-            if constexpr (TWO) need |= pv[t] == UNSET && ps >= r;
-        }
-        if (!__any(need)) break;
-        const uint32_t down = r * sp.stride;
-        int32_t w[T], pw[T];
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            w[t] = (v[t] == UNSET && s >= r) ? lut[e[t] - down] : v[t];
-            if constexpr (TWO) pw[t] = (pv[t] == UNSET && ps >= r) ? lut[pe[t] - down] : pv[t];
-        }
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            v[t] = w[t];
-            if constexpr (TWO) pv[t] = pw[t];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        v[t] = v[t] == UNSET ? 0 : v[t];
-        if constexpr (TWO) pv[t] = pv[t] == UNSET ? 0 : pv[t];
-    }
-}
 
 template <int T>
 __global__ __launch_bounds__(BLOCK) void k_stage_values(const int32_t* __restrict__ lut,
@@ -109,81 +72,6 @@ __global__ __launch_bounds__(BLOCK) void k_stage_values(const int32_t* __restric
     for (int t = 0; t < T; ++t) s += v[t];
     s = group_sum(s);
     if (live && g == 0u) values[i] = s;
-}
-
-// The table pointer of the policy kernel: read-only for act; the TD step's launch writes the
-// promoted entries, so there the const and the __restrict__ go.
-template <bool TD>
-using PolicyLut = std::conditional_t<TD, int32_t*, const int32_t* __restrict__>;
-
-template <int T, bool TD>
-__global__ __launch_bounds__(BLOCK) void k_stage_policy(
-    PolicyLut<TD> lut, const uint4* __restrict__ boards, int64_t n, int64_t* __restrict__ q_out,
-    uint8_t* __restrict__ action_out, uint4* __restrict__ after_out,
-    const uint4* __restrict__ prev, const uint8_t* __restrict__ has_prev, int32_t lr_num,
-    int32_t lr_shift, int32_t* __restrict__ delta_out, int64_t* __restrict__ err_out, Params p,
-    StageParams sp) {
-    const PolicyLane l = policy_lane<BLOCK>(boards, n);
-    const uint32_t st = stage_of(l.s, sp);  // the afterstate's stage: a merge can raise it
-    uint32_t e[T], pe[T];
-    int32_t v[T], pv[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) e[t] = st * sp.stride + entry(p, l.nib, t);
-#pragma unroll
-    for (int t = 0; t < T; ++t) v[t] = l.ok ? lut[e[t]] : 0;
-    bool hp = false, mine = false;  // mine: this lane gathers (and promotes) prev's entries
-    uint32_t pst = 0, unset = 0;
-    if constexpr (TD) {
-        hp = has_prev[l.bi] != 0;
-        mine = hp && l.a == 0u;
-        const Board pb = load_board(prev, l.bi);
-        pst = stage_of(pb, sp);
-        const uint64_t pnib = nibbles(sym(pb, l.g));
-#pragma unroll
-        for (int t = 0; t < T; ++t) pe[t] = pst * sp.stride + entry(p, pnib, t);
-#pragma unroll
-        for (int t = 0; t < T; ++t) pv[t] = mine ? lut[pe[t]] : 0;
-#pragma unroll
-        for (int t = 0; t < T; ++t) unset |= pv[t] == UNSET ? 1u << t : 0u;
-        resolve<T, true>(lut, sp, e, v, st, pe, pv, pst);
-    } else {
-        resolve<T, false>(lut, sp, e, v, st, e, v, st);
-    }
-    int64_t sum = 0, psum = 0;
-#pragma unroll
-    for (int t = 0; t < T; ++t) sum += v[t];
-    sum = group_sum(sum);
-    const Best m = best_move<8>(l.ok ? ((int64_t)l.gain << F) + sum : INT64_MIN, l.lane);
-    if constexpr (TD) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) psum += pv[t];
-        psum = group_sum(psum);  // V(prev) in the group a == 0
-    }
-    if (!l.live) return;
-    if constexpr (TD) {
-        // promotion: the value the entry resolves to, into the entries this lane found UNSET.
-        // `unset` is 0 outside the groups a == 0 of boards with has_prev.
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-            if ((unset >> t) & 1u) lut[pe[t]] = pv[t];
-    }
-    if (q_out != nullptr && (l.lane & 31u) < 4u) {
-        const uint32_t k = l.lane & 3u;
-        q_out[l.i * 4 + k] = k == 0u ? m.q0 : k == 1u ? m.q1 : k == 2u ? m.q2 : m.q3;
-    }
-    if (action_out != nullptr && (l.lane & 31u) == 0u) action_out[l.i] = (uint8_t)m.act;
-    // the lane (a == action, g == 0) holds after(b, action); with no legal move after = b
-    if (after_out != nullptr && l.a == m.act && l.g == 0u) {
-        const Board o = l.legal != 0u ? l.s : l.b;
-        after_out[l.i] = make_uint4(o.r0, o.r1, o.r2, o.r3);
-    }
-    if constexpr (TD) {
-        if ((l.lane & 31u) == 0u) {
-            const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
-            delta_out[l.i] = td.delta;
-            if (err_out != nullptr) err_out[l.i] = td.err;
-        }
-    }
 }
 
 // The update's block, as in g2048_ntuple.hip: 128 boards, their adds summed per entry in an LDS
@@ -232,16 +120,6 @@ __global__ __launch_bounds__(UBLOCK) void k_stage_update(
 
 thread_local std::string g_err;
 
-// the spec, the stage spec and the rest of check_common
-int check_staged(const char* who, const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
-                 const int32_t* lut, const uint8_t* boards, int64_t n) {
-    int rc = check_spec(g_err, who, spec);
-    if (rc != G2048_OK) return rc;
-    rc = check_stages(g_err, who, stages);
-    if (rc != G2048_OK) return rc;
-    return check_common(g_err, who, spec, lut, boards, n);
-}
-
 }  // namespace
 
 extern "C" {
@@ -261,7 +139,7 @@ int64_t g2048_ntstage_lut_entries(const g2048_ntuple_spec* spec,
 int g2048_ntstage_values(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
                          const int32_t* lut_dev, const uint8_t* boards_dev, int64_t n,
                          int64_t* values_out_dev, int device_id, void* stream) {
-    const int rc = check_staged("ntstage_values", spec, stages, lut_dev, boards_dev, n);
+    const int rc = check_staged(g_err, "ntstage_values", spec, stages, lut_dev, boards_dev, n);
     if (rc != G2048_OK) return rc;
     if (values_out_dev == nullptr)
         return refuse(g_err, "ntstage_values: values_out_dev is NULL");
@@ -283,7 +161,7 @@ int g2048_ntstage_act(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* s
                       const int32_t* lut_dev, const uint8_t* boards_dev, int64_t n,
                       int64_t* q_out_dev, uint8_t* action_out_dev, uint8_t* after_out_dev,
                       int device_id, void* stream) {
-    const int rc = check_staged("ntstage_act", spec, stages, lut_dev, boards_dev, n);
+    const int rc = check_staged(g_err, "ntstage_act", spec, stages, lut_dev, boards_dev, n);
     if (rc != G2048_OK) return rc;
     if (q_out_dev == nullptr && action_out_dev == nullptr && after_out_dev == nullptr)
         return refuse(g_err, "ntstage_act: all three outputs are NULL");
@@ -298,9 +176,9 @@ int g2048_ntstage_act(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* s
     const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
     uint4* after = reinterpret_cast<uint4*>(after_out_dev);
     DISPATCH_T(spec->n_tuples,
-               (k_stage_policy<TT, false><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
-                   lut_dev, boards, n, q_out_dev, action_out_dev, after, nullptr, nullptr, 0, 0,
-                   nullptr, nullptr, p, sp)));
+               (k_stage_policy<TT, false><<<policy_grid(n), dim3(POLICY_BLOCK), 0, st>>>(
+                   lut_dev, boards, n, action_out_dev, nullptr, nullptr, 0, 0, nullptr, nullptr, p,
+                   sp, q_out_dev, after)));
     G_HIP(hipGetLastError());
     return G2048_OK;
 }
@@ -311,7 +189,7 @@ int g2048_ntstage_td_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spe
                           int32_t lr_shift, uint8_t* action_out_dev, int32_t* delta_out_dev,
                           int64_t* err_out_dev, int device_id, void* stream) {
     const char* who = "ntstage_td_step";
-    int rc = check_staged(who, spec, stages, lut_dev, boards_dev, n);
+    int rc = check_staged(g_err, who, spec, stages, lut_dev, boards_dev, n);
     if (rc != G2048_OK) return rc;
     rc = check_td_args(g_err, who, prev_dev, has_prev_dev, lr_num, lr_shift, action_out_dev,
                        delta_out_dev, err_out_dev);
@@ -323,9 +201,9 @@ int g2048_ntstage_td_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spe
     const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
     uint4* prev = reinterpret_cast<uint4*>(prev_dev);
     DISPATCH_T(spec->n_tuples,
-               (k_stage_policy<TT, true><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
-                   lut_dev, boards, n, nullptr, action_out_dev, nullptr, prev, has_prev_dev,
-                   lr_num, lr_shift, delta_out_dev, err_out_dev, p, sp)));
+               (k_stage_policy<TT, true><<<policy_grid(n), dim3(POLICY_BLOCK), 0, st>>>(
+                   lut_dev, boards, n, action_out_dev, prev, has_prev_dev, lr_num, lr_shift,
+                   delta_out_dev, err_out_dev, p, sp, nullptr, nullptr)));
     G_HIP(hipGetLastError());
     DISPATCH_T(spec->n_tuples,
                (k_stage_update<TT><<<grid_for(n, UBLOCK / 8), dim3(UBLOCK), 0, st>>>(

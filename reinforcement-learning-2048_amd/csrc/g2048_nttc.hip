@@ -5,8 +5,8 @@
 // bit for bit against tests/nttc_ref.py.  No float anywhere.  The library takes the spec and the
 // table of g2048_ntuple.h and does not link against libg2048_ntuple.so.  What it has in common
 // with g2048_ntuple.hip is g2048_ntuple_dev.hpp's: the index helpers, the policy's lane decode,
-// group sum, argmax and err / delta, the merge table's keys and the prev commit of the update, and
-// the host plumbing and argument checks.  Here are the rate, the (E, A) gather, the hand-over of
+// group sum, argmax and err / delta, the rate, the merge table's keys and the prev commit of the
+// update, and the host plumbing and argument checks.  Here are the (E, A) gather, the hand-over of
 // the steps, the merge table's three sums and the entry points.
 //
 // A step is two launches, because an entry's step depends on its (E, A) from before the call and
@@ -37,7 +37,8 @@
 #ifndef G2048_NTTC_MERGE
 #define G2048_NTTC_MERGE 1
 #endif
-// G2048_NTTC_SLOT_BITS, if defined, fixes log2 of the LDS table's slots for every T (slot_bits)
+// G2048_NTTC_SLOT_BITS, if defined, fixes log2 of the LDS table's slots for every T
+// (tc_slot_bits)
 
 namespace {
 
@@ -46,17 +47,7 @@ using namespace g2048::nt;
 
 constexpr int RATE_BITS = G2048_NTTC_RATE_BITS;
 
-// rate(E, A) of the header.  In the domain (|E| <= A < 2^62) both shifted operands are below 2^16
-// and the divisor is at least 1.
-__host__ __device__ __forceinline__ uint32_t tc_rate(int64_t E, int64_t A) {
-    if (A == 0) return 1u << RATE_BITS;
-    const uint64_t a = (uint64_t)A, e = E < 0 ? 0ull - (uint64_t)E : (uint64_t)E;
-    const int bits = 64 - __builtin_clzll(a);
-    const int s = bits > RATE_BITS ? bits - RATE_BITS : 0;
-    const uint32_t num = (uint32_t)(e >> s) << RATE_BITS, den = (uint32_t)(a >> s);
-    return num / den;
-}
-
+// rate(E, A) of the header is g2048_ntuple_dev.hpp's tc_rate<RATE_BITS>
 __host__ __device__ __forceinline__ int32_t tc_step_of(int32_t delta, uint32_t rate) {
     return (int32_t)(((int64_t)delta * (int64_t)rate) >> RATE_BITS);
 }
@@ -104,7 +95,8 @@ __global__ __launch_bounds__(BLOCK) void k_tc_policy(
     if (mine && td.delta != 0) {
         int32_t* w = work + (l.i * 8 + l.g) * T;
 #pragma unroll
-        for (int t = 0; t < T; ++t) w[t] = tc_step_of(td.delta, tc_rate(pea[t].x, pea[t].y));
+        for (int t = 0; t < T; ++t)
+            w[t] = tc_step_of(td.delta, tc_rate<RATE_BITS>(pea[t].x, pea[t].y));
     }
 }
 
@@ -121,7 +113,7 @@ constexpr int UBLOCK = 1024;
 // to the 4096 slots (96 KiB, one block per CU) that fit a CU's 160 KiB of LDS; on the 2 x 4 set
 // 1024 to 4096 slots differ by less than one run differs from the next, so it keeps 1024.
 template <int T>
-constexpr int slot_bits() {
+constexpr int tc_slot_bits() {
 #ifdef G2048_NTTC_SLOT_BITS
     return G2048_NTTC_SLOT_BITS;
 #else
@@ -133,8 +125,8 @@ constexpr int slot_bits() {
 using u64 = unsigned long long;
 
 // the three adds of one entry, straight to memory
-__device__ __forceinline__ void add_entry(uint32_t* table, u64* ea, uint32_t e, uint32_t step,
-                                          u64 de, u64 da) {
+__device__ __forceinline__ void add_sums(uint32_t* table, u64* ea, uint32_t e, uint32_t step,
+                                         u64 de, u64 da) {
     if (step != 0u) atomicAdd(&table[e], step);
     if (de != 0ull) atomicAdd(&ea[2u * (size_t)e], de);
     atomicAdd(&ea[2u * (size_t)e + 1u], da);
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(UBLOCK) void k_tc_update(
     const uint8_t* __restrict__ action, const int32_t* __restrict__ delta,
     const int32_t* __restrict__ work, Params p) {
 #if G2048_NTTC_MERGE
-    constexpr int SLOT_BITS = slot_bits<T>();
+    constexpr int SLOT_BITS = tc_slot_bits<T>();
     constexpr uint32_t SLOTS = 1u << SLOT_BITS;
     static_assert(SLOTS * 24u <= 160u * 1024u, "the LDS table must fit a CU's 160 KiB");
     __shared__ uint32_t keys[SLOTS];
@@ -188,10 +180,10 @@ __global__ __launch_bounds__(UBLOCK) void k_tc_update(
                 atomicAdd(&esum[slot], de);
                 atomicAdd(&asum[slot], da);
             } else {
-                add_entry(table, ea, e, step, de, da);
+                add_sums(table, ea, e, step, de, da);
             }
 #else
-            add_entry(table, ea, e, step, de, da);
+            add_sums(table, ea, e, step, de, da);
 #endif
         }
     }
@@ -200,7 +192,7 @@ __global__ __launch_bounds__(UBLOCK) void k_tc_update(
 #if G2048_NTTC_MERGE
     for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
         const uint32_t k = keys[s];
-        if (k != NO_KEY) add_entry(table, ea, k, steps[s], esum[s], asum[s]);
+        if (k != NO_KEY) add_sums(table, ea, k, steps[s], esum[s], asum[s]);
     }
 #endif
     if (live && g == 0u) commit_prev(boards, i, action, prev, has_prev);
@@ -220,7 +212,7 @@ int32_t g2048_nttc_rate(int64_t E, int64_t A) {
     if (E > A || E < -A)
         return refuse(g_err, "nttc_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
                       (long long)A);
-    return (int32_t)tc_rate(E, A);
+    return (int32_t)tc_rate<RATE_BITS>(E, A);
 }
 
 int64_t g2048_nttc_work_bytes(const g2048_ntuple_spec* spec, int64_t n) {

@@ -23,10 +23,11 @@
 // The two launches of g2048_ntuple_td_step are the only ordering: the first never writes the
 // table, the second never reads it.
 //
-// g2048_ntuple_dev.hpp holds what this file shares with g2048_nttc.hip and g2048_ntsearch.hip:
-// the index helpers, the policy's lane decode, group sum, argmax and err / delta, the merge
-// table's keys and the prev commit of the update, and the host plumbing and argument checks.
-// Here are the kernels' gathers, the merge table's sums and the entry points.
+// g2048_ntuple_dev.hpp holds what this file shares with the other libraries of the family: the
+// index helpers, the policy's lane decode, group sum, argmax and err / delta, k_policy itself
+// (the batch-mean steps launch it too), the merge table's keys and the prev commit of the update,
+// and the host plumbing and argument checks.  Here are k_values, k_update with the merge table's
+// sums, and the entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -60,53 +61,6 @@ __global__ __launch_bounds__(BLOCK) void k_values(const int32_t* __restrict__ lu
     for (int t = 0; t < T; ++t) s += v[t];
     s = group_sum(s);
     if (live && g == 0u) values[i] = s;
-}
-
-template <int T, bool TD>
-__global__ __launch_bounds__(BLOCK) void k_policy(
-    const int32_t* __restrict__ lut, const uint4* __restrict__ boards, int64_t n,
-    int64_t* __restrict__ q_out, uint8_t* __restrict__ action_out, uint4* __restrict__ after_out,
-    const uint4* __restrict__ prev, const uint8_t* __restrict__ has_prev, int32_t lr_num,
-    int32_t lr_shift, int32_t* __restrict__ delta_out, int64_t* __restrict__ err_out, Params p) {
-    const PolicyLane l = policy_lane<BLOCK>(boards, n);
-    int32_t v[T], pv[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) v[t] = l.ok ? lut[entry(p, l.nib, t)] : 0;
-    bool hp = false;
-    if constexpr (TD) {
-        hp = has_prev[l.bi] != 0;
-        const uint64_t pnib = nibbles(sym(load_board(prev, l.bi), l.g));
-#pragma unroll
-        for (int t = 0; t < T; ++t) pv[t] = (hp && l.a == 0u) ? lut[entry(p, pnib, t)] : 0;
-    }
-    int64_t sum = 0, psum = 0;
-#pragma unroll
-    for (int t = 0; t < T; ++t) sum += v[t];
-    sum = group_sum(sum);
-    const Best m = best_move<8>(l.ok ? ((int64_t)l.gain << F) + sum : INT64_MIN, l.lane);
-    if constexpr (TD) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) psum += pv[t];
-        psum = group_sum(psum);  // V(prev) in the group a == 0
-    }
-    if (!l.live) return;
-    if (q_out != nullptr && (l.lane & 31u) < 4u) {
-        const uint32_t k = l.lane & 3u;
-        q_out[l.i * 4 + k] = k == 0u ? m.q0 : k == 1u ? m.q1 : k == 2u ? m.q2 : m.q3;
-    }
-    if (action_out != nullptr && (l.lane & 31u) == 0u) action_out[l.i] = (uint8_t)m.act;
-    // the lane (a == action, g == 0) holds after(b, action); with no legal move after = b
-    if (after_out != nullptr && l.a == m.act && l.g == 0u) {
-        const Board o = l.legal != 0u ? l.s : l.b;
-        after_out[l.i] = make_uint4(o.r0, o.r1, o.r2, o.r3);
-    }
-    if constexpr (TD) {
-        if ((l.lane & 31u) == 0u) {
-            const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
-            delta_out[l.i] = td.delta;
-            if (err_out != nullptr) err_out[l.i] = td.err;
-        }
-    }
 }
 
 // The update's block: 128 boards.  The boards of a batch share their early-game entries (the
@@ -227,9 +181,9 @@ int g2048_ntuple_act(const g2048_ntuple_spec* spec, const int32_t* lut_dev,
     const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
     uint4* after = reinterpret_cast<uint4*>(after_out_dev);
     DISPATCH_T(spec->n_tuples,
-               (k_policy<TT, false><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
-                   lut_dev, boards, n, q_out_dev, action_out_dev, after, nullptr, nullptr, 0, 0,
-                   nullptr, nullptr, p)));
+               (k_policy<TT, false><<<policy_grid(n), dim3(POLICY_BLOCK), 0, st>>>(
+                   lut_dev, boards, n, action_out_dev, nullptr, nullptr, 0, 0, nullptr, nullptr, p,
+                   q_out_dev, after)));
     G_HIP(hipGetLastError());
     return G2048_OK;
 }
@@ -250,9 +204,9 @@ int g2048_ntuple_td_step(const g2048_ntuple_spec* spec, int32_t* lut_dev, const 
     const uint4* boards = reinterpret_cast<const uint4*>(boards_dev);
     uint4* prev = reinterpret_cast<uint4*>(prev_dev);
     DISPATCH_T(spec->n_tuples,
-               (k_policy<TT, true><<<grid_for(n, BLOCK / 32), dim3(BLOCK), 0, st>>>(
-                   lut_dev, boards, n, nullptr, action_out_dev, nullptr, prev, has_prev_dev,
-                   lr_num, lr_shift, delta_out_dev, err_out_dev, p)));
+               (k_policy<TT, true><<<policy_grid(n), dim3(POLICY_BLOCK), 0, st>>>(
+                   lut_dev, boards, n, action_out_dev, prev, has_prev_dev, lr_num, lr_shift,
+                   delta_out_dev, err_out_dev, p, nullptr, nullptr)));
     G_HIP(hipGetLastError());
     DISPATCH_T(spec->n_tuples, (k_update<TT><<<grid_for(n, UBLOCK / 8), dim3(UBLOCK), 0, st>>>(
                                    lut_dev, boards, n, prev, has_prev_dev, action_out_dev,

@@ -1,14 +1,15 @@
-// g2048_ntuple_dev.hpp -- the one internal header of the n-tuple family: what g2048_ntuple.hip
-// (libg2048_ntuple.so), g2048_ntsearch.hip (libg2048_ntsearch.so) and g2048_nttc.hip
-// (libg2048_nttc.so) share.
+// g2048_ntuple_dev.hpp -- the one internal header of the n-tuple family: what every library that
+// reads the table of include/g2048_ntuple.h shares.
 //   device  board -> table indices (include/g2048_ntuple.h: symmetries, the clamp to 15, idx);
 //           the afterstate policy's lane layout 32s + 8a + g (policy_lane), the sum over a group
 //           (group_sum), the argmax over the four moves (best_move), err and delta (td_error);
-//           the update kernels' LDS merge table (clear_keys, claim_slot) and their common tail
-//           (commit_prev).  The gathers and the payload of the merge table stay in the kernels.
+//           the flat policy kernel itself (k_policy: act, and the first launch of every flat TD
+//           step); the temporal-coherence rate (tc_rate); the update kernels' LDS merge table
+//           (clear_keys, claim_slot) and their common tail (commit_prev).  The update kernels'
+//           gathers and the payload of the merge table stay in the .hip files.
 //   host    the error writer (refuse), G_HIP, DeviceGuard, DISPATCH_T, grid_for, and the
 //           validation of a spec, of the arguments every device entry point has and of those
-//           the two learning steps share (check_spec, check_common, check_td_args).
+//           the learning steps share (check_spec, check_common, check_td_args).
 // Header-only and internal to each library: nothing here is exported, and the libraries do not
 // link against each other.  Each .hip keeps its own thread_local g_err, which G_HIP writes.
 #pragma once
@@ -161,6 +162,81 @@ __device__ __forceinline__ TdError td_error(int64_t best, int64_t psum, bool hp,
     return TdError{err, (int32_t)((err * (int64_t)lr_num) >> lr_shift)};
 }
 
+// The policy kernel: 2 boards per wave, 8 per block of POLICY_BLOCK threads.  A lane's T gathers
+// are all issued before the first is used.  With TD (the first launch of a TD step) the groups
+// a == 0 also gather V(prev) in the same burst, and the launch writes action, delta and err only:
+// q_out and after_out are not looked at, action_out is not null.  Only reads lut.  The TD step's
+// arguments come first, act's two further outputs last: the leading ones arrive preloaded in
+// SGPRs, and the TD launch's argument block is laid out as if the last two were not there.
+// static, as every kernel template of the family's headers: each library has its own copy, as
+// it had of the kernels in its unnamed namespace, and exports no kernel handle.
+constexpr int POLICY_BLOCK = 256;
+
+template <int T, bool TD>
+static __global__ __launch_bounds__(POLICY_BLOCK) void k_policy(
+    const int32_t* __restrict__ lut, const uint4* __restrict__ boards, int64_t n,
+    uint8_t* __restrict__ action_out, const uint4* __restrict__ prev,
+    const uint8_t* __restrict__ has_prev, int32_t lr_num, int32_t lr_shift,
+    int32_t* __restrict__ delta_out, int64_t* __restrict__ err_out, Params p,
+    int64_t* __restrict__ q_out, uint4* __restrict__ after_out) {
+    const PolicyLane l = policy_lane<POLICY_BLOCK>(boards, n);
+    int32_t v[T], pv[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) v[t] = l.ok ? lut[entry(p, l.nib, t)] : 0;
+    bool hp = false;
+    if constexpr (TD) {
+        hp = has_prev[l.bi] != 0;
+        const uint64_t pnib = nibbles(sym(load_board(prev, l.bi), l.g));
+#pragma unroll
+        for (int t = 0; t < T; ++t) pv[t] = (hp && l.a == 0u) ? lut[entry(p, pnib, t)] : 0;
+    }
+    int64_t sum = 0, psum = 0;
+#pragma unroll
+    for (int t = 0; t < T; ++t) sum += v[t];
+    sum = group_sum(sum);
+    const Best m = best_move<8>(l.ok ? ((int64_t)l.gain << F) + sum : INT64_MIN, l.lane);
+    if constexpr (TD) {
+#pragma unroll
+        for (int t = 0; t < T; ++t) psum += pv[t];
+        psum = group_sum(psum);  // V(prev) in the group a == 0
+    }
+    if (!l.live) return;
+    if constexpr (TD) {
+        if ((l.lane & 31u) == 0u) {
+            const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
+            action_out[l.i] = (uint8_t)m.act;
+            delta_out[l.i] = td.delta;
+            if (err_out != nullptr) err_out[l.i] = td.err;
+        }
+    } else {
+        if (q_out != nullptr && (l.lane & 31u) < 4u) {
+            const uint32_t k = l.lane & 3u;
+            q_out[l.i * 4 + k] = k == 0u ? m.q0 : k == 1u ? m.q1 : k == 2u ? m.q2 : m.q3;
+        }
+        if (action_out != nullptr && (l.lane & 31u) == 0u) action_out[l.i] = (uint8_t)m.act;
+        // the lane (a == action, g == 0) holds after(b, action); with no legal move after = b
+        if (after_out != nullptr && l.a == m.act && l.g == 0u) {
+            const Board o = l.legal != 0u ? l.s : l.b;
+            after_out[l.i] = make_uint4(o.r0, o.r1, o.r2, o.r3);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ device: temporal coherence
+// rate(E, A) of include/g2048_nttc.h, g2048_ntmeantc.h and g2048_stagemeantc.h with RATE_BITS
+// fraction bits: each library passes its own header's constant.  In the domain
+// (|E| <= A < 2^62) both shifted operands are below 2^16 and the divisor is at least 1: a 32-bit
+// unsigned division.
+template <int RATE_BITS>
+__host__ __device__ __forceinline__ uint32_t tc_rate(int64_t E, int64_t A) {
+    if (A == 0) return 1u << RATE_BITS;
+    const uint64_t a = (uint64_t)A, e = E < 0 ? 0ull - (uint64_t)E : (uint64_t)E;
+    const int bits = 64 - __builtin_clzll(a);
+    const int s = bits > RATE_BITS ? bits - RATE_BITS : 0;
+    const uint32_t num = (uint32_t)(e >> s) << RATE_BITS, den = (uint32_t)(a >> s);
+    return num / den;
+}
+
 // ------------------------------------------------------------------ device: update kernels
 // The LDS merge table in front of the atomics: the entry index is the key of an open-addressed
 // table of 2^SLOT_BITS slots, linear probing.  Each kernel keeps its payload arrays beside `keys`
@@ -259,6 +335,8 @@ struct DeviceGuard {
 
 // blocks for n boards at `per` boards per block
 inline dim3 grid_for(int64_t n, int per) { return dim3((uint32_t)((n + per - 1) / per)); }
+// the policy kernels' grid: 2 boards per wave
+inline dim3 policy_grid(int64_t n) { return grid_for(n, POLICY_BLOCK / 32); }
 
 // ------------------------------------------------------------------ host: validation
 
@@ -308,7 +386,7 @@ inline int check_common(std::string& err, const char* who, const g2048_ntuple_sp
     return G2048_OK;
 }
 
-// the checks g2048_ntuple_td_step and g2048_nttc_step share past check_common
+// the checks the learning steps share past check_common
 inline int check_td_args(std::string& err, const char* who, const uint8_t* prev,
                          const uint8_t* has_prev, int32_t lr_num, int32_t lr_shift,
                          const uint8_t* action_out, const int32_t* delta_out,

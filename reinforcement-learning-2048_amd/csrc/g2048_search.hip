@@ -109,7 +109,7 @@ __device__ __forceinline__ int64_t move_gain(Board& b, uint32_t a) {
     return (int64_t)g;
 }
 
-__device__ __forceinline__ int64_t floor_div(int64_t num, int32_t den) {  // den > 0
+__device__ __forceinline__ int64_t floor_quot(int64_t num, int32_t den) {  // den > 0
     const int64_t q = num / den;
     return q - (int64_t)(num % den < 0);
 }
@@ -132,7 +132,7 @@ __device__ __forceinline__ int64_t vchance(const Board& s, const Params& p) {
         set_cell(c, bit & 15u, four ? 2u : 1u);
         sum += (int64_t)(four ? p.c4 : p.c2) * vmax<D>(c, p);
     }
-    return floor_div(sum, p.W * max(n, 1));
+    return floor_quot(sum, p.W * max(n, 1));
 }
 
 template <int D>
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(BLOCK) void k_expectimax(const uint4* __restrict__ 
         sum += __shfl_xor(sum, 2);
         sum += __shfl_xor(sum, 1);
         const int32_t ne = __popc(empty_mask(s));
-        const int64_t v = ok ? (int64_t)p.gain * g + floor_div(sum, p.W * max(ne, 1)) : INT64_MIN;
+        const int64_t v = ok ? (int64_t)p.gain * g + floor_quot(sum, p.W * max(ne, 1)) : INT64_MIN;
         const int64_t v0 = __shfl(v, 0), v1 = __shfl(v, 16), v2 = __shfl(v, 32), v3 = __shfl(v, 48);
         // smallest a with the largest value; an illegal move holds INT64_MIN and a legal move's
         // value is far above it, so with no legal move the action stays 0

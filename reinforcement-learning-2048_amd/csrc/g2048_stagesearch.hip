@@ -73,7 +73,7 @@ __device__ __forceinline__ uint32_t empties(const Board& b) {
     return m;
 }
 
-__device__ __forceinline__ int64_t floor_div(int64_t num, int32_t den) {  // den > 0
+__device__ __forceinline__ int64_t floor_quot(int64_t num, int32_t den) {  // den > 0
     const int64_t q = num / den;
     return q - (int64_t)(num % den < 0);
 }
@@ -205,7 +205,7 @@ __device__ __forceinline__ int64_t vafter(const int32_t* __restrict__ lut, const
             set_cell(c, bit & 15u, four ? 2u : 1u);
             sum += (int64_t)(four ? p.c4 : p.c2) * vmax<D>(lut, p, c);
         }
-        return floor_div(sum, p.W * max((int32_t)__popc(em), 1));
+        return floor_quot(sum, p.W * max((int32_t)__popc(em), 1));
     }
 }
 
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(BLOCK) void k_stagesearch(const int32_t* __restrict
             }
             sum = row_sum<ROW>(sum);  // the chance node of move a
             const int32_t ne = __popc(empties(s));
-            v = ok ? ((int64_t)gain << F) + floor_div(sum, p.W * max(ne, 1)) : INT64_MIN;
+            v = ok ? ((int64_t)gain << F) + floor_quot(sum, p.W * max(ne, 1)) : INT64_MIN;
         }
         const Best m = best_move<ROW>(v, lane);
         if (!live) continue;

@@ -163,14 +163,16 @@ def test_build_keeps_the_new_source_out_of_the_other_stamps():
 def test_stamp_follows_its_source_the_shared_header_and_the_three_public_headers(tmp_path,
                                                                                  monkeypatch):
     """A change to the new source changes only the new stamp -- the main library's does not move;
-    a change to the shared csrc header changes the new stamp too; a change to each of g2048.h,
+    a change to the batch-mean header changes the new stamp and none of the other nine; a change
+    to the shared csrc header changes the new stamp too; a change to each of g2048.h,
     g2048_ntuple.h and g2048_ntmean.h changes the new stamp, the last one no other."""
     import shutil
 
     import __graft_entry__ as G
 
-    assert f'#include "{G.NTUPLE_SHARED[0]}"' in \
-        open(os.path.join(G.CSRC, G.NTMEAN_SRCS[0])).read()
+    src = open(os.path.join(G.CSRC, G.NTMEAN_SRCS[0])).read()
+    assert f'#include "{G.NTUPLE_SHARED[0]}"' in src and f'#include "{G.NTMEAN_SHARED[0]}"' in src
+    assert not re.search(r'#include\s+"[^"]*\.hip"', src)
     before = _hashes(G)
     copy = str(tmp_path / "csrc")
     shutil.copytree(G.CSRC, copy)
@@ -180,10 +182,14 @@ def test_stamp_follows_its_source_the_shared_header_and_the_three_public_headers
         f.write("// changed\n")
     after = _hashes(G)
     assert after[:9] == before[:9] and after[9] != before[9]
+    with open(os.path.join(copy, G.NTMEAN_SHARED[0]), "a") as f:
+        f.write("// changed\n")
+    mean = _hashes(G)
+    assert mean[:9] == before[:9] and mean[9] != after[9]
     with open(os.path.join(copy, G.NTUPLE_SHARED[0]), "a") as f:
         f.write("// changed\n")
     shared = _hashes(G)
-    assert shared[0] == before[0] and shared[9] != after[9] and shared[2] != before[2]
+    assert shared[0] == before[0] and shared[9] != mean[9] and shared[2] != before[2]
     last, include = shared, os.path.join(G.ROOT, "include")
     for k, header in enumerate(("g2048.h", "g2048_ntuple.h", "g2048_ntmean.h")):
         root = str(tmp_path / f"root{k}")
@@ -196,6 +202,34 @@ def test_stamp_follows_its_source_the_shared_header_and_the_three_public_headers
         if header == "g2048_ntmean.h":
             assert now[:9] == shared[:9]
         last = now
+
+
+ONE_DEFINITION = ("resolve", "tc_rate", "floor_div", "add_entry", "slot_bits", "check_staged",
+                  "k_mean_gather", "k_mean_apply", "k_policy", "k_stage_policy")
+
+
+def test_the_shared_device_code_is_defined_in_one_file():
+    """The fall-through, the rate, the quotient, the (D, C) add, the slot counts, the staged
+    checks and the gather, apply, flat-policy and staged-policy kernel templates each have one
+    definition under csrc/: a return type, the name and an opening parameter list, comments
+    aside."""
+    import __graft_entry__ as G
+
+    texts = {}
+    for f in sorted(os.listdir(G.CSRC)):
+        with open(os.path.join(G.CSRC, f)) as fh:
+            texts[f] = re.sub(r"//[^\n]*", "", fh.read())
+    for name in ONE_DEFINITION:
+        rx = re.compile(r"\b(?:void|int|int64_t|uint32_t)\s+%s\s*\(" % name)
+        found = {f: len(rx.findall(t)) for f, t in texts.items() if rx.search(t)}
+        assert len(found) == 1 and list(found.values()) == [1], (name, found)
+    where = {name: f for name in ONE_DEFINITION for f, t in texts.items()
+             if re.search(r"\b(?:void|int|int64_t|uint32_t)\s+%s\s*\(" % name, t)}
+    assert {where[n] for n in ("k_policy", "tc_rate")} == {G.NTUPLE_SHARED[0]}
+    assert {where[n] for n in ("resolve", "check_staged", "k_stage_policy")} == \
+        {G.NTSTAGE_SHARED[0]}
+    assert {where[n] for n in ("floor_div", "add_entry", "slot_bits", "k_mean_gather",
+                               "k_mean_apply")} == {G.NTMEAN_SHARED[0]}
 
 
 def _spec(tuples, n_tuples=None, n_cells=None):

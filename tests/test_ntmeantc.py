@@ -306,17 +306,18 @@ def test_build_keeps_the_new_source_out_of_the_other_stamps():
 
 def test_stamp_follows_its_source_the_shared_header_and_the_three_public_headers(tmp_path,
                                                                                  monkeypatch):
-    """A change to the new source changes only the new stamp; a change to the shared csrc header
-    changes the new stamp too; a change to each of g2048.h, g2048_ntuple.h and g2048_ntmeantc.h
-    changes the new stamp, the last one no other."""
+    """A change to the new source changes only the new stamp; a change to the batch-mean header
+    changes the three batch-mean stamps and none of the other nine; a change to the shared csrc
+    header changes the new stamp too; a change to each of g2048.h, g2048_ntuple.h and
+    g2048_ntmeantc.h changes the new stamp, the last one no other."""
     import shutil
 
     import __graft_entry__ as G
 
     src = open(os.path.join(G.CSRC, G.NTMEANTC_SRCS[0])).read()
     assert f'#include "{G.NTUPLE_SHARED[0]}"' in src
-    # the restated bodies come from the two originals, which the source does not include
-    assert "g2048_ntmean.hip" in src and "g2048_nttc.hip" in src
+    # the batch-mean step and the rate come from the shared headers, not from another source
+    assert f'#include "{G.NTMEAN_SHARED[0]}"' in src
     assert not re.search(r'#include\s+"[^"]*\.hip"', src)
     before = _hashes(G)
     copy = str(tmp_path / "csrc")
@@ -327,10 +328,14 @@ def test_stamp_follows_its_source_the_shared_header_and_the_three_public_headers
         f.write("// changed\n")
     after = _hashes(G)
     assert after[:11] == before[:11] and after[11] != before[11]
+    with open(os.path.join(copy, G.NTMEAN_SHARED[0]), "a") as f:
+        f.write("// changed\n")
+    mean = _hashes(G)
+    assert mean[:9] == before[:9] and all(mean[k] != after[k] for k in (9, 10, 11))
     with open(os.path.join(copy, G.NTUPLE_SHARED[0]), "a") as f:
         f.write("// changed\n")
     shared = _hashes(G)
-    assert shared[0] == before[0] and shared[11] != after[11] and shared[2] != before[2]
+    assert shared[0] == before[0] and shared[11] != mean[11] and shared[2] != before[2]
     last, include = shared, os.path.join(G.ROOT, "include")
     for k, header in enumerate(("g2048.h", "g2048_ntuple.h", "g2048_ntmeantc.h")):
         root = str(tmp_path / f"root{k}")

@@ -265,15 +265,18 @@ def test_build_keeps_the_new_source_out_of_the_other_stamps():
 
 def test_stamp_follows_its_source_the_shared_headers_and_the_four_public_headers(tmp_path,
                                                                                  monkeypatch):
-    """A change to the new source changes only the new stamp; a change to either shared csrc
-    header changes the new stamp too; a change to each of g2048.h, g2048_ntuple.h, g2048_ntstage.h
-    and g2048_stagemean.h changes the new stamp, the last one no other."""
+    """A change to the new source changes only the new stamp; a change to the batch-mean header
+    changes the two batch-mean stamps and none of the other nine; a change to either other shared
+    csrc header changes the new stamp too; a change to each of g2048.h, g2048_ntuple.h,
+    g2048_ntstage.h and g2048_stagemean.h changes the new stamp, the last one no other."""
     import shutil
 
     import __graft_entry__ as G
 
     src = open(os.path.join(G.CSRC, G.STAGEMEAN_SRCS[0])).read()
-    assert f'#include "{G.NTUPLE_SHARED[0]}"' in src and f'#include "{G.NTSTAGE_SHARED[0]}"' in src
+    for shared in (G.NTUPLE_SHARED[0], G.NTSTAGE_SHARED[0], G.NTMEAN_SHARED[0]):
+        assert f'#include "{shared}"' in src
+    assert not re.search(r'#include\s+"[^"]*\.hip"', src)
     before = _hashes(G)
     copy = str(tmp_path / "csrc")
     shutil.copytree(G.CSRC, copy)
@@ -283,7 +286,10 @@ def test_stamp_follows_its_source_the_shared_headers_and_the_four_public_headers
         f.write("// changed\n")
     after = _hashes(G)
     assert after[:10] == before[:10] and after[10] != before[10]
-    last = after
+    with open(os.path.join(copy, G.NTMEAN_SHARED[0]), "a") as f:
+        f.write("// changed\n")
+    last = _hashes(G)
+    assert last[:9] == before[:9] and last[9] != after[9] and last[10] != after[10]
     for shared, also in ((G.NTUPLE_SHARED[0], 2), (G.NTSTAGE_SHARED[0], 6)):
         with open(os.path.join(copy, shared), "a") as f:
             f.write("// changed\n")

@@ -426,9 +426,10 @@ def test_build_keeps_the_new_source_out_of_the_other_stamps():
 def test_stamp_follows_its_source_the_shared_headers_and_the_four_public_headers(tmp_path,
                                                                                  monkeypatch):
     """A change to the new source changes only the new stamp -- source_hash() included, which
-    lists the file among the sources with stamps of their own; a change to either shared csrc
-    header changes the new stamp too; a change to each of g2048.h, g2048_ntuple.h, g2048_ntstage.h
-    and g2048_stagemeantc.h changes the new stamp, the last one no other."""
+    lists the file among the sources with stamps of their own; a change to the batch-mean header
+    changes exactly the four batch-mean stamps; a change to either other shared csrc header
+    changes the new stamp too; a change to each of g2048.h, g2048_ntuple.h, g2048_ntstage.h and
+    g2048_stagemeantc.h changes the new stamp, the last one no other."""
     import shutil
 
     import __graft_entry__ as G
@@ -436,9 +437,7 @@ def test_stamp_follows_its_source_the_shared_headers_and_the_four_public_headers
     src = open(os.path.join(G.CSRC, G.STAGEMEANTC_SRCS[0])).read()
     includes = re.findall(r'#include\s+"([^"]+)"', src)
     assert includes == ["../../include/g2048_stagemeantc.h", "g2048_board.hpp", G.NTUPLE_SHARED[0],
-                        G.NTSTAGE_SHARED[0]]
-    # the restated bodies come from the three originals, which the source does not include
-    assert all(name in src for name in ("g2048_ntstage.hip", "g2048_ntmean.hip", "g2048_nttc.hip"))
+                        G.NTSTAGE_SHARED[0], G.NTMEAN_SHARED[0]]
     before = _hashes(G)
     copy = str(tmp_path / "csrc")
     shutil.copytree(G.CSRC, copy)
@@ -448,7 +447,10 @@ def test_stamp_follows_its_source_the_shared_headers_and_the_four_public_headers
         f.write("// changed\n")
     after = _hashes(G)
     assert after[:12] == before[:12] and after[12] != before[12]
-    last = after
+    with open(os.path.join(copy, G.NTMEAN_SHARED[0]), "a") as f:
+        f.write("// changed\n")
+    last = _hashes(G)
+    assert last[:9] == before[:9] and all(last[k] != after[k] for k in (9, 10, 11, 12))
     for shared, also in ((G.NTUPLE_SHARED[0], 2), (G.NTSTAGE_SHARED[0], 6),
                          ("g2048_board.hpp", 1)):
         with open(os.path.join(copy, shared), "a") as f:

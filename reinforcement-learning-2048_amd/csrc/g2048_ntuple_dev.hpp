@@ -1,5 +1,7 @@
-// g2048_ntuple_dev.hpp -- the one internal header of the n-tuple family: what every library that
-// reads the table of include/g2048_ntuple.h shares.
+// g2048_ntuple_dev.hpp -- the base internal header of the n-tuple family: what every library that
+// reads the table of include/g2048_ntuple.h shares.  The narrower shared headers build on it:
+// g2048_ntstage_dev.hpp (the stage rule), g2048_ntmean_dev.hpp (the batch-mean step) and
+// g2048_ntsearch_dev.hpp (the expectimax tree walk).
 //   device  board -> table indices (include/g2048_ntuple.h: symmetries, the clamp to 15, idx);
 //           the afterstate policy's lane layout 32s + 8a + g (policy_lane), the sum over a group
 //           (group_sum), the argmax over the four moves (best_move), err and delta (td_error);

@@ -183,6 +183,55 @@ def test_shared_header_is_in_both_stamps_and_not_in_the_main_one(tmp_path, monke
     assert after[:2] == before[:2] and after[2] != before[2] and after[3] != before[3]
 
 
+def _all_hashes(G):
+    return (G.source_hash(), G.search_source_hash(), G.ntuple_source_hash(),
+            G.ntsearch_source_hash(), G.nttc_source_hash(), G.ntlambda_source_hash(),
+            G.ntstage_source_hash(), G.stagesearch_source_hash(), G.ntrestart_source_hash(),
+            G.ntmean_source_hash(), G.stagemean_source_hash(), G.ntmeantc_source_hash(),
+            G.stagemeantc_source_hash())
+
+
+def test_tree_walk_header_is_in_the_two_search_stamps_and_in_no_other(tmp_path, monkeypatch):
+    """The expectimax tree lives in one csrc header that both search sources include: a change to
+    it changes the stamps of libg2048_ntsearch.so and libg2048_stagesearch.so and of none of the
+    other libraries."""
+    import shutil
+
+    import __graft_entry__ as G
+
+    assert G.NTSEARCH_SHARED == ("g2048_ntsearch_dev.hpp",)
+    for src in G.NTSEARCH_SRCS + G.STAGESEARCH_SRCS:
+        assert f'#include "{G.NTSEARCH_SHARED[0]}"' in open(os.path.join(G.CSRC, src)).read()
+    shared = open(os.path.join(G.CSRC, G.NTSEARCH_SHARED[0])).read()
+    assert G.NTSTAGE_SHARED[0] not in re.sub(r"//[^\n]*", "", shared)
+    before = _all_hashes(G)
+    assert len(set(before)) == 13
+    copy = str(tmp_path / "csrc")
+    shutil.copytree(G.CSRC, copy)
+    monkeypatch.setattr(G, "CSRC", copy)
+    assert _all_hashes(G) == before
+    with open(os.path.join(copy, G.NTSEARCH_SHARED[0]), "a") as f:
+        f.write("// changed\n")
+    after = _all_hashes(G)
+    assert {k for k in range(13) if after[k] != before[k]} == {3, 7}
+
+
+def test_both_sources_include_the_one_copy_of_the_tree_walk():
+    """The tree (vmax, vafter, leaf_value), its helpers and the kernel are defined once, in the
+    shared header, and in neither search source; the sources define no kernel at all."""
+    import __graft_entry__ as G
+
+    shared = open(os.path.join(G.CSRC, G.NTSEARCH_SHARED[0])).read()
+    for src in G.NTSEARCH_SRCS + G.STAGESEARCH_SRCS:
+        text = open(os.path.join(G.CSRC, src)).read()
+        assert f'#include "{G.NTSEARCH_SHARED[0]}"' in text
+        for name in ("int64_t vmax(", "int64_t vafter(", "int64_t leaf_value(",
+                     "int64_t floor_quot(", "uint32_t empties(", "uint64_t flip_rows(",
+                     "uint64_t flip_cols(", "int64_t row_sum(", "void k_search("):
+            assert name in shared and name not in text, (src, name)
+        assert "__global__" not in text, src
+
+
 def test_kernel_has_no_store_data_hazard(tmp_path):
     """tools/store_hazard_audit.py over the library's source, compiled with the library's
     flags, as tests/test_ntuple.py audits the n-tuple library's."""

@@ -237,9 +237,11 @@ def test_stamps_follow_the_new_files(tmp_path, monkeypatch):
     assert own[:7] == before[:7] and own[7] != before[7]
     rule = touch(os.path.join(copy, G.NTSTAGE_SHARED[0]))
     assert rule[:6] == before[:6] and rule[6] != own[6] and rule[7] != own[7]
+    tree = touch(os.path.join(copy, G.NTSEARCH_SHARED[0]))  # the two searches' tree walk
+    assert {k for k in range(8) if tree[k] != rule[k]} == {3, 7}
     family = touch(os.path.join(copy, G.NTUPLE_SHARED[0]))
     assert family[:2] == before[:2]
-    assert all(family[k] != rule[k] for k in range(2, 8))
+    assert all(family[k] != tree[k] for k in range(2, 8))
     root = str(tmp_path / "root")
     shutil.copytree(os.path.join(real_root, "include"), os.path.join(root, "include"))
     monkeypatch.setattr(G, "ROOT", root)

@@ -132,7 +132,8 @@ def main():
                 med = statistics.median(ms)
                 row = {"set": name, "table_bytes": net.lut.numel() * 4, "boards": n, "call": what,
                        "depth": depth, "us_median": med * 1e3, "us_min": min(ms) * 1e3,
-                       "us_max": max(ms) * 1e3, "reps": len(ms), "mean_empty_cells": empties,
+                       "us_max": max(ms) * 1e3, "us": [m * 1e3 for m in ms], "reps": len(ms),
+                       "mean_empty_cells": empties,
                        "leaves_per_board": leaves, "boards_per_s": n / (med * 1e-3),
                        "leaves_per_s": n * leaves / (med * 1e-3),
                        "gathers_per_s": n * leaves * 8 * T / (med * 1e-3)}

@@ -24,6 +24,7 @@ resolved(0) and over resolved(S - 1): mean score, mean moves, max-tile counts, w
 
     python tools/stagesearch_bench.py [--mode time] [--sets 2x4 4x6] [--sizes 1024 65536]
                                       [--depths 1 2 3] [--bound 6] [--out FILE]
+                                      [--lib OTHER_BUILD.so] [--ntsearch-lib OTHER_BUILD.so]
     python tools/stagesearch_bench.py --mode strength [--nets 2x4 4x6:11] [--seconds 60]
 """
 from __future__ import annotations
@@ -105,6 +106,8 @@ def time_mode(args, torch, g2048):
                            "single_us_median": med["single"] * 1e3,
                            "single_us_min": min(ms["single"]) * 1e3,
                            "single_us_max": max(ms["single"]) * 1e3, "reps": args.reps,
+                           "us": [m * 1e3 for m in ms["staged"]],
+                           "single_us": [m * 1e3 for m in ms["single"]],
                            "ratio": med["staged"] / med["single"],
                            # the identities: S = 1 and the lifted table search as the single one
                            "equal_to_single": bool(torch.equal(out[0][1], out[1][1]))}
@@ -118,7 +121,8 @@ def time_mode(args, torch, g2048):
                           f"{row['equal_to_single']}", flush=True)
         del net, configs, trained
         torch.cuda.empty_cache()
-    return {"play": args.play, "p4": args.p4, "bound": args.bound,
+    return {"play": args.play, "p4": args.p4, "bound": args.bound, "lib": args.lib,
+            "ntsearch_lib": args.ntsearch_lib,
             "train_steps": args.train_steps, "train_boards": args.train_boards, "rows": rows}
 
 
@@ -207,6 +211,11 @@ def main():
     ap.add_argument("--steps", type=int, default=4000, help="strength, 2x4: training steps")
     ap.add_argument("--seconds", type=float, default=60.0, help="strength, 4x6: training time")
     ap.add_argument("--games", type=int, default=256)
+    ap.add_argument("--lib", default=None,
+                    help="time another build of libg2048_stagesearch.so (such as the parent "
+                         "commit's, or one with -DG2048_STAGESEARCH_LEAF_TUPLES=3)")
+    ap.add_argument("--ntsearch-lib", default=None,
+                    help="another build of libg2048_ntsearch.so, the library it alternates with")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.seed is None:
@@ -218,6 +227,10 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("stagesearch_bench needs a GPU")
+    if args.lib:
+        g2048.stagesearch.LIB_PATH = os.path.abspath(args.lib)
+    if args.ntsearch_lib:
+        g2048.ntsearch.LIB_PATH = os.path.abspath(args.ntsearch_lib)
     g2048.stagesearch.load()
     out = {"time": time_mode, "strength": strength_mode}[args.mode](args, torch, g2048)
     if args.out:

@@ -1,12 +1,14 @@
 // g2048_ntsearch_dev.hpp -- the expectimax tree walk over an n-tuple value network, shared by the
-// two search libraries: g2048_ntsearch.hip (one table) and g2048_stagesearch.hip (a staged table).
+// search libraries: g2048_ntsearch.hip (one table), g2048_stagesearch.hip (a staged table) and
+// g2048_deepsearch.hip (either, one tree over many waves).
 // One copy, so the chance node, the tie rule and the grid-stride loop cannot drift.
 //   device  the tree (vmax, vafter, leaf_value), the kernel (k_search) and the flat leaf (FlatLeaf)
 //   host    everything of an entry point after the checks of its spec, table and boards
 //           (search_launch)
 // Header-only and internal to each library, as g2048_ntuple_dev.hpp: nothing here is exported.
-// The staged leaf needs g2048_ntstage_dev.hpp and so lives in g2048_stagesearch.hip, not here:
-// the flat library does not follow the stage header.
+// The staged leaf needs g2048_ntstage_dev.hpp and so lives in g2048_stageleaf_dev.hpp, not here:
+// the flat library does not follow the stage header.  g2048_deepsearch.hip builds its own kernels
+// on the same tree (vmax, vafter, the leaf policies) and launches k_search through search_launch.
 //
 // The search is defined in include/g2048_ntsearch.h; every value is an int64.  No float anywhere.
 //

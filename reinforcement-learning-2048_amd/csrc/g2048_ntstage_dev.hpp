@@ -9,7 +9,7 @@
 //   host    the validation of a stage spec (check_stages, check_staged) and the params struct
 //           (StageParams, make_stage_params)
 // Below the root the search keeps a fall-through of its own, a per-lane loop over a burst
-// (g2048_stagesearch.hip's StagedLeaf); at depth 1, where whole waves reach the leaf, it calls
+// (g2048_stageleaf_dev.hpp's StagedLeaf); at depth 1, where whole waves reach the leaf, it calls
 // resolve.  It instantiates no kernel template of this header.
 // Header-only and internal to each library, as g2048_ntuple_dev.hpp: nothing here is exported.
 #pragma once

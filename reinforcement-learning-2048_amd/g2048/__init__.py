@@ -5,7 +5,7 @@ src/dqn_lib.py): the env step, replay buffer and train_step, batched over tens o
 boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI include/g2048.h).
 """
 from ._native import NativeError, load as load_native  # noqa: F401
-from . import (ntlambda, ntmean, ntmeantc, ntrestart, ntsearch, ntstage, nttc,  # noqa: F401
+from . import (deepsearch, ntlambda, ntmean, ntmeantc, ntrestart, ntsearch, ntstage, nttc,  # noqa: F401
                ntuple, search, stagemean, stagemeantc, stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
@@ -30,4 +30,4 @@ __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIO
            "ntmean", "MeanState", "MeanTrainer", "default_mean_lr_shift",
            "stagemean", "StagedMeanState", "StagedMeanTrainer",
            "ntmeantc", "MeanTCState", "MeanTCTrainer", "default_meantc_lr_shift",
-           "stagemeantc", "StagedMeanTCState", "StagedMeanTCTrainer"]
+           "stagemeantc", "StagedMeanTCState", "StagedMeanTCTrainer", "deepsearch"]

@@ -222,6 +222,15 @@ class NTupleNetwork:
         return ntsearch.expectimax(self, boards, depth, p4, values, actions, values_out,
                                    actions_out)
 
+    def deep_search(self, boards: torch.Tensor, depth: int = 4, p4: float = 0.5, top=None,
+                    values=True, actions=True, values_out=None, actions_out=None):
+        """The same search 1..5 moves deep with the top `top` moves spread over many waves
+        (g2048.deepsearch.expectimax): (actions u8 [n], values i64 [n, 4])."""
+        from . import deepsearch
+
+        return deepsearch.expectimax(self, boards, depth, p4, top, values, actions, values_out,
+                                     actions_out)
+
     def td_step(self, boards, prev, has_prev, lr_num, lr_shift, actions_out, delta_out,
                 err_out=None):
         """One TD(0) step of the header on caller-owned state and outputs (no allocation)."""

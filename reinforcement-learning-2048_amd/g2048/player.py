@@ -26,6 +26,11 @@ Policies (one game per board, every board plays to its end):
            ntuple=StagedNTupleNetwork, search_depth 1..3, the player's p4): every leaf is valued
            at its own stage.  Depth 1 is the ntuple policy of that network.  Always a legal move;
            history tuples as play_game's.
+  ntuple_deep / ntstage_deep  the same two searches through g2048.deepsearch (ntuple=net or
+           ntuple=StagedNTupleNetwork, the player's p4): search_depth 1..4 player moves deep, the
+           top of every tree spread over many waves (deepsearch.default_top).  At depths 1..3
+           they play the games of ntuple_search / ntstage_search.  Always a legal move; history
+           tuples as play_game's.
 
 Results follow the reference's bookkeeping: `moves` = steps taken (history length, terminal
 step included), `merge_score`, `max_tile`; `max_tile_frequency()` is notebook_utils'
@@ -37,7 +42,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import ntsearch, ntstage, qnet, search, stagesearch
+from . import deepsearch, ntsearch, ntstage, qnet, search, stagesearch
 from .env import VecEnv2048
 from .nets import Conv2048
 
@@ -197,10 +202,20 @@ class BatchedPlayer:
             if self.search_depth > stagesearch.MAX_DEPTH:
                 raise ValueError(f"the ntstage_search policy searches 1..{stagesearch.MAX_DEPTH} "
                                  f"moves deep (search_depth = {self.search_depth})")
+        if policy in ("ntuple_deep", "ntstage_deep"):
+            want = "StagedNTupleNetwork" if policy == "ntstage_deep" else "NTupleNetwork"
+            if self.ntuple is None:
+                raise ValueError(f"the {policy} policy needs a network (ntuple={want})")
+            if isinstance(self.ntuple, ntstage.StagedNTupleNetwork) != (policy == "ntstage_deep"):
+                raise TypeError(f"the {policy} policy takes a {want}")
+            if self.search_depth > deepsearch.MAX_DEPTH:
+                raise ValueError(f"the {policy} policy searches 1..{deepsearch.MAX_DEPTH} "
+                                 f"moves deep (search_depth = {self.search_depth})")
         if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple", "ntuple_search",
-                          "ntstage_search"):
+                          "ntstage_search", "ntuple_deep", "ntstage_deep"):
             raise ValueError("policy must be 'random', 'upleft', 'greedy', 'expectimax', "
-                             "'ntuple', 'ntuple_search' or 'ntstage_search'")
+                             "'ntuple', 'ntuple_search', 'ntstage_search', 'ntuple_deep' or "
+                             "'ntstage_deep'")
         env = self._env(egreedy="fixed" if policy == "random" else "compat")
         dev = self.device
         n = self.n
@@ -247,6 +262,12 @@ class BatchedPlayer:
             elif policy == "ntstage_search":
                 act, _ = stagesearch.expectimax(self.ntuple, env.board, self.search_depth,
                                                 self.p4, values=False)
+                reward, done, _ = env.step(act)
+                ended = done.bool()
+                newly_stuck = None
+            elif policy in ("ntuple_deep", "ntstage_deep"):
+                act, _ = deepsearch.expectimax(self.ntuple, env.board, self.search_depth,
+                                               self.p4, values=False)
                 reward, done, _ = env.step(act)
                 ended = done.bool()
                 newly_stuck = None

@@ -6,7 +6,7 @@ boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI 
 """
 from ._native import NativeError, load as load_native  # noqa: F401
 from . import (deepsearch, ntlambda, ntmean, ntmeantc, ntrestart, ntsearch, ntstage, nttc,  # noqa: F401
-               ntuple, search, stagemean, stagemeantc, stagesearch)
+               ntuple, search, stagedelay, stagemean, stagemeantc, stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
                      generate_replay_buffer_using_expectimax)
@@ -20,6 +20,7 @@ from .ntmean import MeanState, MeanTrainer, default_mean_lr_shift  # noqa: F401
 from .stagemean import StagedMeanState, StagedMeanTrainer  # noqa: F401
 from .ntmeantc import MeanTCState, MeanTCTrainer, default_meantc_lr_shift  # noqa: F401
 from .stagemeantc import StagedMeanTCState, StagedMeanTCTrainer  # noqa: F401
+from .stagedelay import DelayedLambdaState, DelayedLambdaTrainer  # noqa: F401
 
 __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIONS", "NativeError",
            "load_native", "search", "SearchWeights", "expectimax",
@@ -30,4 +31,5 @@ __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIO
            "ntmean", "MeanState", "MeanTrainer", "default_mean_lr_shift",
            "stagemean", "StagedMeanState", "StagedMeanTrainer",
            "ntmeantc", "MeanTCState", "MeanTCTrainer", "default_meantc_lr_shift",
-           "stagemeantc", "StagedMeanTCState", "StagedMeanTCTrainer", "deepsearch"]
+           "stagemeantc", "StagedMeanTCState", "StagedMeanTCTrainer", "deepsearch",
+           "stagedelay", "DelayedLambdaState", "DelayedLambdaTrainer"]

@@ -6,7 +6,7 @@ boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI 
 """
 from ._native import NativeError, load as load_native  # noqa: F401
 from . import (deepsearch, ntlambda, ntmean, ntmeantc, ntrestart, ntsearch, ntstage, nttc,  # noqa: F401
-               ntuple, search, stagedelay, stagemean, stagemeantc, stagesearch)
+               ntuple, search, stageback, stagedelay, stagemean, stagemeantc, stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
                      generate_replay_buffer_using_expectimax)
@@ -21,6 +21,7 @@ from .stagemean import StagedMeanState, StagedMeanTrainer  # noqa: F401
 from .ntmeantc import MeanTCState, MeanTCTrainer, default_meantc_lr_shift  # noqa: F401
 from .stagemeantc import StagedMeanTCState, StagedMeanTCTrainer  # noqa: F401
 from .stagedelay import DelayedLambdaState, DelayedLambdaTrainer  # noqa: F401
+from .stageback import BackwardState, BackwardTrainer  # noqa: F401
 
 __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIONS", "NativeError",
            "load_native", "search", "SearchWeights", "expectimax",
@@ -32,4 +33,5 @@ __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIO
            "stagemean", "StagedMeanState", "StagedMeanTrainer",
            "ntmeantc", "MeanTCState", "MeanTCTrainer", "default_meantc_lr_shift",
            "stagemeantc", "StagedMeanTCState", "StagedMeanTCTrainer", "deepsearch",
-           "stagedelay", "DelayedLambdaState", "DelayedLambdaTrainer"]
+           "stagedelay", "DelayedLambdaState", "DelayedLambdaTrainer",
+           "stageback", "BackwardState", "BackwardTrainer"]

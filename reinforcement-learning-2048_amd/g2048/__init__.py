@@ -5,8 +5,8 @@ src/dqn_lib.py): the env step, replay buffer and train_step, batched over tens o
 boards per launch on gfx950.  Native code: csrc/g2048.hip -> libg2048.so (C ABI include/g2048.h).
 """
 from ._native import NativeError, load as load_native  # noqa: F401
-from . import (deepsearch, ntlambda, ntmean, ntmeantc, ntrestart, ntsearch, ntstage, nttc,  # noqa: F401
-               ntuple, search, stageback, stagedelay, stagemean, stagemeantc, stagesearch)
+from . import (deepsearch, ntlambda, ntmean, ntmeantc, ntplay, ntrestart, ntsearch, ntstage,  # noqa: F401
+               nttc, ntuple, search, stageback, stagedelay, stagemean, stagemeantc, stagesearch)
 from .env import ACTIONS, EpisodeLog, ReplayBuffer, VecEnv2048, decode_episodes  # noqa: F401
 from .search import (SearchWeights, expectimax,  # noqa: F401
                      generate_replay_buffer_using_expectimax)
@@ -34,4 +34,4 @@ __all__ = ["VecEnv2048", "ReplayBuffer", "EpisodeLog", "decode_episodes", "ACTIO
            "ntmeantc", "MeanTCState", "MeanTCTrainer", "default_meantc_lr_shift",
            "stagemeantc", "StagedMeanTCState", "StagedMeanTCTrainer", "deepsearch",
            "stagedelay", "DelayedLambdaState", "DelayedLambdaTrainer",
-           "stageback", "BackwardState", "BackwardTrainer"]
+           "stageback", "BackwardState", "BackwardTrainer", "ntplay"]

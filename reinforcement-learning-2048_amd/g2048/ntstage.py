@@ -209,6 +209,13 @@ class StagedNTupleNetwork:
         return deepsearch.expectimax(self, boards, depth, p4, top, values, actions, values_out,
                                      actions_out)
 
+    def play_steps(self, env, k: int, depth: int = 1, fin=None, result=None) -> None:
+        """k moves of the depth-`depth` policy of these tables on every board of `env`, inside
+        one launch (g2048.ntplay.steps), every leaf at its own stage.  The table is only read."""
+        from . import ntplay
+
+        ntplay.steps(self, env, k, depth, fin, result)
+
     def td_step(self, boards, prev, has_prev, lr_num, lr_shift, actions_out, delta_out,
                 err_out=None):
         """One TD(0) step of the header, promotion included, on caller-owned state and outputs

@@ -31,6 +31,10 @@ Policies (one game per board, every board plays to its end):
            top of every tree spread over many waves (deepsearch.default_top).  At depths 1..3
            they play the games of ntuple_search / ntstage_search.  Always a legal move; history
            tuples as play_game's.
+  ntuple_fused / ntstage_fused  the games of ntuple_search / ntstage_search (of ntuple at
+           search_depth 1), played on the device: one g2048.ntplay.steps call of check_every
+           moves per iteration instead of a policy launch and an env step per move.  search_depth
+           1..3, the player's p4.  No per-move trace is kept, so record_games > 0 is refused.
 
 Results follow the reference's bookkeeping: `moves` = steps taken (history length, terminal
 step included), `merge_score`, `max_tile`; `max_tile_frequency()` is notebook_utils'
@@ -42,7 +46,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import deepsearch, ntsearch, ntstage, qnet, search, stagesearch
+from . import deepsearch, ntplay, ntsearch, ntstage, qnet, search, stagesearch
 from .env import VecEnv2048
 from .nets import Conv2048
 
@@ -211,11 +215,24 @@ class BatchedPlayer:
             if self.search_depth > deepsearch.MAX_DEPTH:
                 raise ValueError(f"the {policy} policy searches 1..{deepsearch.MAX_DEPTH} "
                                  f"moves deep (search_depth = {self.search_depth})")
+        if policy in ("ntuple_fused", "ntstage_fused"):
+            want = "StagedNTupleNetwork" if policy == "ntstage_fused" else "NTupleNetwork"
+            if self.ntuple is None:
+                raise ValueError(f"the {policy} policy needs a network (ntuple={want})")
+            if isinstance(self.ntuple, ntstage.StagedNTupleNetwork) != (policy == "ntstage_fused"):
+                raise TypeError(f"the {policy} policy takes a {want}")
+            if self.search_depth > ntplay.MAX_DEPTH:
+                raise ValueError(f"the {policy} policy searches 1..{ntplay.MAX_DEPTH} "
+                                 f"moves deep (search_depth = {self.search_depth})")
+            if self.record:
+                raise ValueError(f"the {policy} policy keeps no per-move trace "
+                                 "(record_games must be 0)")
+            return self._play_fused(policy)
         if policy not in ("random", "upleft", "greedy", "expectimax", "ntuple", "ntuple_search",
                           "ntstage_search", "ntuple_deep", "ntstage_deep"):
             raise ValueError("policy must be 'random', 'upleft', 'greedy', 'expectimax', "
-                             "'ntuple', 'ntuple_search', 'ntstage_search', 'ntuple_deep' or "
-                             "'ntstage_deep'")
+                             "'ntuple', 'ntuple_search', 'ntstage_search', 'ntuple_deep', "
+                             "'ntstage_deep', 'ntuple_fused' or 'ntstage_fused'")
         env = self._env(egreedy="fixed" if policy == "random" else "compat")
         dev = self.device
         n = self.n
@@ -302,6 +319,27 @@ class BatchedPlayer:
                           f_moves.cpu().numpy(), stuck.cpu().numpy(), hist)
         res.trace = rec
         return res
+
+    def _play_fused(self, policy: str) -> GameResults:
+        """The fused policies: check_every moves per ntplay.steps call, the last call shortened
+        to max_moves; a game's result is the ep row of its first terminal step."""
+        env = self._env()
+        n, dev = self.n, self.device
+        fin = torch.zeros(n, dtype=torch.uint8, device=dev)
+        result = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        t = 0
+        while True:  # at least one move, as the move-by-move loop
+            k = max(1, min(self.check_every, self.max_moves - t, ntplay.MAX_STEPS))
+            ntplay.steps(self.ntuple, env, k, self.search_depth, fin, result)
+            t += k
+            if bool(fin.all()) or t >= self.max_moves:
+                break
+        env.check_errors()
+        r = result.to(torch.int64) & 0xFFFFFFFF  # u32 words held in int32
+        f_max = r[:, 3]
+        max_tile = torch.where(f_max > 0, torch.ones_like(f_max) << f_max, f_max)
+        return GameResults(policy, max_tile.cpu().numpy(), r[:, 1].cpu().numpy(),
+                           r[:, 2].cpu().numpy(), torch.zeros(n, dtype=torch.bool).numpy(), [])
 
     @staticmethod
     def _histories(policy, rec, moves):

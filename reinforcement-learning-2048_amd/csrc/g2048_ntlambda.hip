@@ -5,9 +5,9 @@
 // checked bit for bit against tests/ntlambda_ref.py.  No float anywhere.  The library takes the
 // spec and the table of g2048_ntuple.h and does not link against libg2048_ntuple.so.  What it has
 // in common with g2048_ntuple.hip is g2048_ntuple_dev.hpp's: the index helpers, the policy's lane
-// decode, group sum, argmax and err / delta, the merge table's keys, and the host plumbing and
-// argument checks.  Here are the ring of afterstates, the walk over it with the shifted deltas,
-// its commit and the entry points.
+// decode, group sum, argmax and err / delta, the merge table's keys, the clamped ring position
+// (which g2048_stagedelay.hip reads too), and the host plumbing and argument checks.  Here are
+// the walk over the ring of afterstates with the shifted deltas, its commit and the entry points.
 //
 // A step is two launches, ordered as in TD(0): the first never writes lut, the second never reads
 // it.
@@ -47,18 +47,6 @@ using namespace g2048::nt;
 
 constexpr int MAXH = G2048_NTLAMBDA_MAX_HORIZON;
 constexpr int BLOCK = 256;
-
-// The ring position of a board, clamped into the domain (head < H, depth <= H) so that a state
-// the caller corrupted cannot index past the planes.
-struct Ring {
-    uint32_t head, depth;
-};
-
-__device__ __forceinline__ Ring load_ring(const uint8_t* __restrict__ head,
-                                          const uint8_t* __restrict__ depth, int64_t i,
-                                          uint32_t H) {
-    return Ring{min((uint32_t)head[i], H - 1u), min((uint32_t)depth[i], H)};
-}
 
 template <int T>
 __global__ __launch_bounds__(BLOCK) void k_lam_policy(

@@ -1,14 +1,18 @@
-// g2048_ntmean_dev.hpp -- the batch-mean step, shared by the four libraries that run it:
-// g2048_ntmean.hip, g2048_stagemean.hip, g2048_ntmeantc.hip and g2048_stagemeantc.hip.  One copy,
-// so the owner exchange cannot drift between them.
+// g2048_ntmean_dev.hpp -- the batch-mean step, shared by the six libraries that run it:
+// g2048_ntmean.hip, g2048_stagemean.hip, g2048_ntmeantc.hip, g2048_stagemeantc.hip,
+// g2048_stagedelay.hip and g2048_stageback.hip.  One copy, so the owner exchange cannot drift
+// between them.
 //   device  the (D, C) gather (k_mean_gather) and the apply with its owner exchange
 //           (k_mean_apply), each once, over two small by-value objects:
 //             Index  how an entry index is formed: FlatIndex, entry(p, nib, t) alone, or
 //                    g2048_ntstage_dev.hpp's StagedIndex, which adds stage(prev) * stride
 //             Tail   what the owner of an entry does with m = floor(D / C): MeanTail adds m into
 //                    the table, TcTail scales m by rate(E, A) and updates (E, A)
-//   host    the checks of acc and ea (check_acc, check_ea), their size (table_bytes) and the
-//           three launches of a step (mean_step)
+//           A library whose hits come from elsewhere (a ring, a trajectory) writes kernels of its
+//           own around the same pieces: the gather table's hit and flush (gather_hit,
+//           gather_flush), add_entry, apply_entry and the tails.
+//   host    the three launches of a step (mean_step); the checks of acc and ea and their size
+//           stand in g2048_ntuple_dev.hpp
 // Header-only and internal to each library, as g2048_ntuple_dev.hpp: nothing here is exported.
 //
 // Why three launches.  An entry moves by floor(D / C) over ALL hits of the step, and nothing
@@ -94,21 +98,53 @@ __device__ __forceinline__ void add_entry(u64* acc, uint32_t e, u64 d, u64 c) {
     atomicAdd(&acc[2u * (size_t)e + 1u], c);
 }
 
-// 8 boards per wave, 128 per block: lane g re-forms its T entries of idx(prev, g, .).  Per block
-// the two sums of an entry are first merged in an LDS hash table and each used slot is flushed
-// with two 64-bit atomic adds; a hit without a slot after four probes adds straight to memory.
+// The gather's table, over the three LDS arrays the kernel declares (2^slot_bits<T>() slots each):
+// per block the two sums of an entry are first merged in an LDS hash table and each used slot is
+// flushed with two 64-bit atomic adds; a hit without a slot after four probes adds straight to
+// memory.  A kernel clears the arrays, has every board-lane add its T hits (gather_hit) and
+// flushes (gather_flush), with a barrier of its own on either side of the hits.  Only these two
+// are functions: they compile to the text the kernels had with the code written out.  The clear,
+// the loop over a lane's T entries and the apply's whole frame do not -- a function that holds
+// them is simplified before it is inlined, and the kernel around it comes out in another order
+// (profiles/tcfamily/README.md) -- so each kernel keeps those lines.
+template <int T>
+constexpr uint32_t gather_slots() {
+    static_assert((16u << slot_bits<T>()) <= 160u * 1024u, "the LDS table must fit a CU's 160 KiB");
+    return 1u << slot_bits<T>();
+}
+
+// one hit: (de, 1) into entry e
+template <int T>
+__device__ __forceinline__ void gather_hit(uint32_t* keys, uint32_t* csum, u64* dsum, u64* acc,
+                                           uint32_t e, u64 de) {
+    const uint32_t slot = claim_slot<slot_bits<T>()>(keys, e);
+    if (slot != NO_SLOT) {
+        atomicAdd(&dsum[slot], de);
+        atomicAdd(&csum[slot], 1u);
+    } else {
+        add_entry(acc, e, de, 1ull);
+    }
+}
+
+template <int T>
+__device__ __forceinline__ void gather_flush(const uint32_t* keys, const uint32_t* csum,
+                                             const u64* dsum, u64* acc) {
+    for (uint32_t s = threadIdx.x; s < gather_slots<T>(); s += UBLOCK) {
+        const uint32_t k = keys[s];
+        if (k != NO_KEY) add_entry(acc, k, dsum[s], (u64)csum[s]);
+    }
+}
+
+// 8 boards per wave, 128 per block: lane g re-forms its T entries of idx(prev, g, .).
 template <int T, typename Index>
 static __global__ __launch_bounds__(UBLOCK) void k_mean_gather(
     int64_t* __restrict__ acc_, int64_t n, const uint4* __restrict__ prev,
     const uint8_t* __restrict__ has_prev, const int32_t* __restrict__ delta, Params p, Index ix) {
-    constexpr int SLOT_BITS = slot_bits<T>();
-    constexpr uint32_t SLOTS = 1u << SLOT_BITS;
-    static_assert(SLOTS * 16u <= 160u * 1024u, "the LDS table must fit a CU's 160 KiB");
-    __shared__ uint32_t keys[SLOTS];
-    __shared__ uint32_t csum[SLOTS];
-    __shared__ u64 dsum[SLOTS];
-    clear_keys<SLOT_BITS, UBLOCK>(keys);
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
+    __shared__ uint32_t keys[gather_slots<T>()];
+    __shared__ uint32_t csum[gather_slots<T>()];
+    __shared__ u64 dsum[gather_slots<T>()];
+    clear_keys<slot_bits<T>(), UBLOCK>(keys);
+    for (uint32_t s = threadIdx.x; s < gather_slots<T>(); s += UBLOCK) {
         csum[s] = 0u;
         dsum[s] = 0ull;
     }
@@ -124,22 +160,11 @@ static __global__ __launch_bounds__(UBLOCK) void k_mean_gather(
         const uint64_t nib = nibbles(sym(pb, g));
         const u64 de = (u64)(int64_t)d;
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const uint32_t e = base + entry(p, nib, t);
-            const uint32_t slot = claim_slot<SLOT_BITS>(keys, e);
-            if (slot != NO_SLOT) {
-                atomicAdd(&dsum[slot], de);
-                atomicAdd(&csum[slot], 1u);
-            } else {
-                add_entry(acc, e, de, 1ull);
-            }
-        }
+        for (int t = 0; t < T; ++t)
+            gather_hit<T>(keys, csum, dsum, acc, base + entry(p, nib, t), de);
     }
     __syncthreads();
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
-        const uint32_t k = keys[s];
-        if (k != NO_KEY) add_entry(acc, k, dsum[s], (u64)csum[s]);
-    }
+    gather_flush<T>(keys, csum, dsum, acc);
 }
 
 // ------------------------------------------------------------------ device: apply
@@ -208,30 +233,6 @@ static __global__ __launch_bounds__(UBLOCK) void k_mean_apply(
 }
 
 // ------------------------------------------------------------------ host
-// bytes of acc, and of ea: 16 per entry of every stage
-inline int64_t table_bytes(const g2048_ntuple_spec& spec, int n_stages = 1) {
-    return (int64_t)n_stages * ((int64_t)spec.n_tuples << (4 * spec.n_cells)) * 2 *
-           (int64_t)sizeof(int64_t);
-}
-
-inline int check_acc(std::string& err, const char* who, const int64_t* acc) {
-    if (acc == nullptr) return refuse(err, "%s: acc_dev is NULL", who);
-    if (((uintptr_t)acc & 15u) != 0) return refuse(err, "%s: acc_dev must be 16-byte aligned", who);
-    return G2048_OK;
-}
-
-// acc and ea are two tables of `bytes` each: the same one, or two that share a part, would hand
-// the exchanges of (D, C) an entry's (E, A)
-inline int check_ea(std::string& err, const char* who, const int64_t* ea, const int64_t* acc,
-                    int64_t bytes) {
-    if (ea == nullptr) return refuse(err, "%s: ea_dev is NULL", who);
-    if (((uintptr_t)ea & 15u) != 0) return refuse(err, "%s: ea_dev must be 16-byte aligned", who);
-    const uintptr_t a = (uintptr_t)acc, b = (uintptr_t)ea;
-    if ((a < b ? b - a : a - b) < (uintptr_t)bytes)
-        return refuse(err, "%s: ea_dev overlaps acc_dev", who);
-    return G2048_OK;
-}
-
 // the TD policy launch that goes with an index; g2048_ntstage_dev.hpp has StagedIndex's
 template <int T>
 inline void launch_td_policy(const FlatIndex&, hipStream_t st, int32_t* lut, const uint4* boards,

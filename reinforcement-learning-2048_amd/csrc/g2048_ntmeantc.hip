@@ -36,12 +36,7 @@ extern "C" {
 const char* g2048_ntmeantc_last_error(void) { return g_err.c_str(); }
 
 int32_t g2048_ntmeantc_rate(int64_t E, int64_t A) {
-    if (A < 0 || A > G2048_NTMEANTC_MAX_A)
-        return refuse(g_err, "ntmeantc_rate: A = %lld outside [0, 2^62)", (long long)A);
-    if (E > A || E < -A)
-        return refuse(g_err, "ntmeantc_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
-                      (long long)A);
-    return (int32_t)tc_rate<RATE_BITS>(E, A);
+    return checked_rate<RATE_BITS, G2048_NTMEANTC_MAX_A>(g_err, "ntmeantc_rate", E, A);
 }
 
 int64_t g2048_ntmeantc_acc_bytes(const g2048_ntuple_spec* spec) {

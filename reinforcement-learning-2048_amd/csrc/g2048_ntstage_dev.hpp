@@ -1,13 +1,16 @@
 // g2048_ntstage_dev.hpp -- the stage rule of include/g2048_ntstage.h, shared by the libraries
-// that read a staged table: g2048_ntstage.hip, g2048_stagesearch.hip, g2048_stagemean.hip and
-// g2048_stagemeantc.hip.  One copy, so they cannot drift.
+// that read a staged table: g2048_ntstage.hip, g2048_stagesearch.hip, g2048_stagemean.hip,
+// g2048_stagemeantc.hip, g2048_stagedelay.hip and g2048_stageback.hip.  One copy, so they cannot
+// drift.
 //   device  M(b) on the board in registers (max_tile), stage(b) against the bounds bytes of the
 //           params struct (stage_of); the staged entry index of the batch-mean kernels
 //           (StagedIndex); the learners' fall-through, a wave vote over one or two sets of T
-//           entries (resolve); the staged policy kernel with its promotion (k_stage_policy: act,
-//           and the first launch of every staged TD step)
-//   host    the validation of a stage spec (check_stages, check_staged) and the params struct
-//           (StageParams, make_stage_params)
+//           entries (resolve); the promotion store of every staged TD policy (promote); the
+//           staged policy kernel (k_stage_policy: act, and the first launch of the staged TD
+//           steps that keep prev / has_prev)
+//   host    the validation of a stage spec (check_stages, check_staged), the params struct
+//           (StageParams, make_stage_params), and what the staged batch-mean libraries' entry
+//           points open with (staged_acc_bytes, check_staged_tc)
 // Below the root the search keeps a fall-through of its own, a per-lane loop over a burst
 // (g2048_stageleaf_dev.hpp's StagedLeaf); at depth 1, where whole waves reach the leaf, it calls
 // resolve.  It instantiates no kernel template of this header.
@@ -110,6 +113,28 @@ __device__ __forceinline__ void resolve(LUT lut, const StageParams& sp, const ui
     }
 }
 
+// ------------------------------------------------------------------ device: promotion
+// The promotion store, shared by the staged TD policies (k_stage_policy<T, true> here,
+// k_delay_policy, k_back_policy).  Each kernel forms and loads its two sets of T entries, takes
+// the mask of the UNSET ones and sums the values itself: a function that holds those loops is
+// simplified before it is inlined (the loads of Params move to the kernel's entry, the sums
+// associate another way) and the kernel comes out in another order, act's instantiation
+// included (profiles/tcfamily/README.md).
+// Promotion: the value the entry resolves to, into the entries that `unset` names (0 in a lane
+// that promotes nothing).
+// Promotion needs no ordering.  The only table words the launch writes are UNSET entries, each
+// with the value it resolves to in the pre-call table, so any lane that reads one, before or after
+// the store, resolves to the same number, and two lanes that promote one entry store the same
+// number.  Every entry a later launch of the step adds into was promoted here, so those launches
+// never land on UNSET and never read the table.
+template <int T>
+__device__ __forceinline__ void promote(int32_t* lut, const uint32_t (&e)[T],
+                                        const int32_t (&v)[T], uint32_t unset) {
+#pragma unroll
+    for (int t = 0; t < T; ++t)
+        if ((unset >> t) & 1u) lut[e[t]] = v[t];
+}
+
 // The table pointer of the policy kernel: read-only for act; the TD step's launch writes the
 // promoted entries, so there the const and the __restrict__ go.
 template <bool TD>
@@ -119,11 +144,6 @@ using PolicyLut = std::conditional_t<TD, int32_t*, const int32_t* __restrict__>;
 // gather V(prev) at stage(prev) in the same fall-through rounds and store the promoted values,
 // and the launch writes action, delta and err only: q_out and after_out are not looked at,
 // action_out is not null.
-// Promotion needs no ordering.  The only table words the launch writes are UNSET entries, each
-// with the value it resolves to in the pre-call table, so any lane that reads one, before or after
-// the store, resolves to the same number, and two lanes that promote one entry store the same
-// number.  Every entry a later launch of the step adds into was promoted here, so those launches
-// never land on UNSET and never read the table.
 template <int T, bool TD>
 static __global__ __launch_bounds__(POLICY_BLOCK) void k_stage_policy(
     PolicyLut<TD> lut, const uint4* __restrict__ boards, int64_t n,
@@ -169,11 +189,8 @@ static __global__ __launch_bounds__(POLICY_BLOCK) void k_stage_policy(
     }
     if (!l.live) return;
     if constexpr (TD) {
-        // promotion: the value the entry resolves to, into the entries this lane found UNSET.
-        // `unset` is 0 outside the groups a == 0 of boards with has_prev.
-#pragma unroll
-        for (int t = 0; t < T; ++t)
-            if ((unset >> t) & 1u) lut[pe[t]] = pv[t];
+        // `unset` is 0 outside the groups a == 0 of boards with has_prev
+        promote(lut, pe, pv, unset);
         if ((l.lane & 31u) == 0u) {
             const TdError td = td_error(m.best, psum, hp, l.legal, lr_num, lr_shift);
             action_out[l.i] = (uint8_t)m.act;
@@ -236,6 +253,28 @@ inline int check_staged(std::string& err, const char* who, const g2048_ntuple_sp
     rc = check_stages(err, who, stages);
     if (rc != G2048_OK) return rc;
     return check_common(err, who, spec, lut, boards, n);
+}
+
+// what every exported *_acc_bytes of a staged library returns
+inline int64_t staged_acc_bytes(std::string& err, const char* who, const g2048_ntuple_spec* spec,
+                                const g2048_ntstage_spec* stages) {
+    int rc = check_spec(err, who, spec);
+    if (rc != G2048_OK) return rc;
+    rc = check_stages(err, who, stages);
+    if (rc != G2048_OK) return rc;
+    return table_bytes(*spec, stages->n_stages);
+}
+
+// check_staged, then acc and ea beside the staged table: how every staged mean-TC step opens
+inline int check_staged_tc(std::string& err, const char* who, const g2048_ntuple_spec* spec,
+                           const g2048_ntstage_spec* stages, const int32_t* lut,
+                           const uint8_t* boards, int64_t n, const int64_t* acc,
+                           const int64_t* ea) {
+    int rc = check_staged(err, who, spec, stages, lut, boards, n);
+    if (rc != G2048_OK) return rc;
+    rc = check_acc(err, who, acc);
+    if (rc != G2048_OK) return rc;
+    return check_ea(err, who, ea, acc, table_bytes(*spec, stages->n_stages));
 }
 
 inline StageParams make_stage_params(const g2048_ntuple_spec& spec,

@@ -7,11 +7,14 @@
 //           (group_sum), the argmax over the four moves (best_move), err and delta (td_error);
 //           the flat policy kernel itself (k_policy: act, and the first launch of every flat TD
 //           step); the temporal-coherence rate (tc_rate); the update kernels' LDS merge table
-//           (clear_keys, claim_slot) and their common tail (commit_prev).  The update kernels'
-//           gathers and the payload of the merge table stay in the .hip files.
+//           (clear_keys, claim_slot) and their common tail (commit_prev); the ring position of
+//           the two ring libraries (Ring, load_ring, plane_back).  The update kernels' gathers
+//           and the payload of the merge table stay in the .hip files.
 //   host    the error writer (refuse), G_HIP, DeviceGuard, DISPATCH_T, grid_for, and the
 //           validation of a spec, of the arguments every device entry point has and of those
-//           the learning steps share (check_spec, check_common, check_td_args).
+//           the learning steps share (check_spec, check_common, check_td_args), of a device
+//           pointer (check_ptr), of (E, A) in front of the rate (checked_rate) and of the
+//           batch-mean step's acc and ea (table_bytes, check_acc, check_ea).
 // Header-only and internal to each library: nothing here is exported, and the libraries do not
 // link against each other.  Each .hip keeps its own thread_local g_err, which G_HIP writes.
 #pragma once
@@ -286,6 +289,25 @@ __device__ __forceinline__ void commit_prev(const uint4* __restrict__ boards, in
     has_prev[i] = any ? 1 : 0;
 }
 
+// ------------------------------------------------------------------ device: the ring
+// The ring libraries (g2048_ntlambda.hip, g2048_stagedelay.hip) keep a board's last H afterstates
+// in H planes of n rows.  The ring position of a board, clamped into the domain (head < H,
+// depth <= H) so that a state the caller corrupted cannot index past the planes.
+struct Ring {
+    uint32_t head, depth;
+};
+
+__device__ __forceinline__ Ring load_ring(const uint8_t* __restrict__ head,
+                                          const uint8_t* __restrict__ depth, int64_t i,
+                                          uint32_t H) {
+    return Ring{min((uint32_t)head[i], H - 1u), min((uint32_t)depth[i], H)};
+}
+
+// the plane k steps back from `head`, k < H
+__device__ __forceinline__ uint32_t plane_back(uint32_t head, uint32_t k, uint32_t H) {
+    return head >= k ? head - k : head + H - k;
+}
+
 // ------------------------------------------------------------------ host: errors and launches
 // Each library keeps its own thread-local message; these write the reason into `err`.
 inline int refuse(std::string& err, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -409,6 +431,52 @@ inline int check_td_args(std::string& err, const char* who, const uint8_t* prev,
         return refuse(err, "%s: delta_out_dev must be 4-byte aligned", who);
     if (((uintptr_t)err_out & 7u) != 0)
         return refuse(err, "%s: err_out_dev must be 8-byte aligned", who);
+    return G2048_OK;
+}
+
+// a device pointer with its alignment, a power of two
+inline int check_ptr(std::string& err, const char* who, const char* name, const void* ptr,
+                     unsigned align) {
+    if (ptr == nullptr) return refuse(err, "%s: %s is NULL", who, name);
+    if (((uintptr_t)ptr & (uintptr_t)(align - 1u)) != 0)
+        return refuse(err, "%s: %s must be %u-byte aligned", who, name, align);
+    return G2048_OK;
+}
+
+// what every exported *_rate returns: rate(E, A) in the domain, a refusal outside it.  Each
+// library passes its own header's RATE_BITS and MAX_A.
+template <int RATE_BITS, int64_t MAX_A>
+inline int32_t checked_rate(std::string& err, const char* who, int64_t E, int64_t A) {
+    static_assert(MAX_A == ((int64_t)1 << 62) - 1, "the message below says 2^62");
+    if (A < 0 || A > MAX_A)
+        return refuse(err, "%s: A = %lld outside [0, 2^62)", who, (long long)A);
+    if (E > A || E < -A)
+        return refuse(err, "%s: |E| = |%lld| exceeds A = %lld", who, (long long)E, (long long)A);
+    return (int32_t)tc_rate<RATE_BITS>(E, A);
+}
+
+// ------------------------------------------------------------------ host: acc and ea
+// The batch-mean step's two tables beside lut (g2048_ntmean_dev.hpp).  Their checks stand here so
+// that g2048_ntstage_dev.hpp can run them behind its own.
+// bytes of acc, and of ea: 16 per entry of every stage
+inline int64_t table_bytes(const g2048_ntuple_spec& spec, int n_stages = 1) {
+    return (int64_t)n_stages * ((int64_t)spec.n_tuples << (4 * spec.n_cells)) * 2 *
+           (int64_t)sizeof(int64_t);
+}
+
+inline int check_acc(std::string& err, const char* who, const int64_t* acc) {
+    return check_ptr(err, who, "acc_dev", acc, 16);
+}
+
+// acc and ea are two tables of `bytes` each: the same one, or two that share a part, would hand
+// the exchanges of (D, C) an entry's (E, A)
+inline int check_ea(std::string& err, const char* who, const int64_t* ea, const int64_t* acc,
+                    int64_t bytes) {
+    const int rc = check_ptr(err, who, "ea_dev", ea, 16);
+    if (rc != G2048_OK) return rc;
+    const uintptr_t a = (uintptr_t)acc, b = (uintptr_t)ea;
+    if ((a < b ? b - a : a - b) < (uintptr_t)bytes)
+        return refuse(err, "%s: ea_dev overlaps acc_dev", who);
     return G2048_OK;
 }
 

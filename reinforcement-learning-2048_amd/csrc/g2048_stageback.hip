@@ -7,8 +7,8 @@
 // of the project.
 //
 // What it shares with the family is the headers': the policy's lane decode, group sum, argmax and
-// err (g2048_ntuple_dev.hpp), the stage of a board, the fall-through and the staged index
-// (g2048_ntstage_dev.hpp), the (D, C) gather, the owner exchange and the temporal-coherence tail
+// err (g2048_ntuple_dev.hpp), the stage of a board, the fall-through, the promotion store and
+// the staged index (g2048_ntstage_dev.hpp), the (D, C) gather, the owner exchange and the temporal-coherence tail
 // (g2048_ntmean_dev.hpp).  Here are the two trajectory buffers of a board with their counters and
 // the two kernels that the headers do not have:
 //   k_back_policy  k_stage_policy's frame, 32 lanes per board.  Lane 0 of a board reads its four
@@ -25,6 +25,10 @@
 // and written by that board's 32 lanes alone, all in one wave, every load before the first store,
 // and the buffer read ((cur & 1) ^ 1) is never the buffer written (cur & 1).  L is a run-time
 // value; T is a template parameter.
+// The two kernels keep the lines they have in common with k_stage_policy<T, true>
+// and k_mean_apply written out.  Only what compiles to the same text either way is
+// a function of the headers; the rest, put into one, reschedules the kernel around it
+// (profiles/tcfamily/README.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -110,11 +114,9 @@ __global__ __launch_bounds__(POLICY_BLOCK) void k_back_policy(
     psum = group_sum(psum);                      // V(x) in the group a == 0, V(y) in a == 1
     const int64_t vy = __shfl(psum, first + 8);  // V(y), or 0 without a successor
     if (!l.live) return;
-    // promotion: the value the entry resolves to, into the entries of x this lane found UNSET.
-    // `unset` is 0 outside the groups a == 0 of replaying boards.
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-        if ((unset >> t) & 1u) lut[pe[t]] = pv[t];
+    // x's entries that this lane found UNSET: `unset` is 0 outside the groups a == 0 of
+    // replaying boards
+    promote(lut, pe, pv, unset);
     // record: this lane holds after(b, action) and gain(b, action)
     if (l.legal != 0u && l.a == m.act && l.g == 0u) {
         const int64_t at = slot_row(l.i, c_cur, c_rec % L, L);
@@ -192,13 +194,6 @@ int check_horizon(const char* who, int64_t n, int32_t horizon) {
     return G2048_OK;
 }
 
-int check_ptr(const char* who, const char* name, const void* ptr, unsigned align) {
-    if (ptr == nullptr) return refuse(g_err, "%s: %s is NULL", who, name);
-    if (((uintptr_t)ptr & (uintptr_t)(align - 1u)) != 0)
-        return refuse(g_err, "%s: %s must be %u-byte aligned", who, name, align);
-    return G2048_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -206,22 +201,12 @@ extern "C" {
 const char* g2048_stageback_last_error(void) { return g_err.c_str(); }
 
 int32_t g2048_stageback_rate(int64_t E, int64_t A) {
-    if (A < 0 || A > G2048_STAGEBACK_MAX_A)
-        return refuse(g_err, "stageback_rate: A = %lld outside [0, 2^62)", (long long)A);
-    if (E > A || E < -A)
-        return refuse(g_err, "stageback_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
-                      (long long)A);
-    return (int32_t)tc_rate<RATE_BITS>(E, A);
+    return checked_rate<RATE_BITS, G2048_STAGEBACK_MAX_A>(g_err, "stageback_rate", E, A);
 }
 
 int64_t g2048_stageback_acc_bytes(const g2048_ntuple_spec* spec,
                                   const g2048_ntstage_spec* stages) {
-    const char* who = "stageback_acc_bytes";
-    int rc = check_spec(g_err, who, spec);
-    if (rc != G2048_OK) return rc;
-    rc = check_stages(g_err, who, stages);
-    if (rc != G2048_OK) return rc;
-    return table_bytes(*spec, stages->n_stages);
+    return staged_acc_bytes(g_err, "stageback_acc_bytes", spec, stages);
 }
 
 int64_t g2048_stageback_traj_bytes(int64_t n, int32_t horizon) {
@@ -242,11 +227,7 @@ int g2048_stageback_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spec
                          uint8_t* x_out_dev, uint8_t* replay_out_dev, int64_t* err_out_dev,
                          int device_id, void* stream) {
     const char* who = "stageback_step";
-    int rc = check_staged(g_err, who, spec, stages, lut_dev, boards_dev, n);
-    if (rc != G2048_OK) return rc;
-    rc = check_acc(g_err, who, acc_dev);
-    if (rc != G2048_OK) return rc;
-    rc = check_ea(g_err, who, ea_dev, acc_dev, table_bytes(*spec, stages->n_stages));
+    int rc = check_staged_tc(g_err, who, spec, stages, lut_dev, boards_dev, n, acc_dev, ea_dev);
     if (rc != G2048_OK) return rc;
     rc = check_horizon(who, n, horizon);
     if (rc != G2048_OK) return rc;
@@ -259,7 +240,7 @@ int g2048_stageback_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spec
                 {"rep_n_dev", rep_n_dev, 4},  {"rep_k_dev", rep_k_dev, 4},
                 {"x_out_dev", x_out_dev, 16}, {"replay_out_dev", replay_out_dev, 1}};
     for (const auto& q : ptrs) {
-        rc = check_ptr(who, q.name, q.ptr, q.align);
+        rc = check_ptr(g_err, who, q.name, q.ptr, q.align);
         if (rc != G2048_OK) return rc;
     }
     // x_out and replay_out stand where prev and has_prev stand: checked above, so what is left of

@@ -6,9 +6,10 @@
 // spec, the stage spec and the table of g2048_ntstage.h and does not link against another library
 // of the project.
 //
-// What it shares with the family is the headers': the policy's lane decode, group sum, argmax and
-// err (g2048_ntuple_dev.hpp), the stage of a board, the fall-through and the staged index
-// (g2048_ntstage_dev.hpp), the (D, C) add, the owner exchange and the temporal-coherence tail
+// What it shares with the family is the headers': the policy's lane decode, group sum, argmax,
+// err and the clamped ring position (g2048_ntuple_dev.hpp), the stage of a board, the
+// fall-through, the promotion store and the staged index (g2048_ntstage_dev.hpp), the gather
+// table's hit and flush, the (D, C) add, the owner exchange and the temporal-coherence tail
 // (g2048_ntmean_dev.hpp).  Here are the ring of afterstates with its error sums and the three
 // kernels that walk it:
 //   k_delay_policy  g2048_ntstage_dev.hpp's k_stage_policy<T, true> with prev read through the
@@ -28,6 +29,10 @@
 // a block of terminal boards makes up to H times the keys, and what finds no slot goes the
 // direct way, which is correct at any load.  H and s are run-time values; T is a template
 // parameter.
+// The three kernels keep the lines they have in common with k_stage_policy<T, true>,
+// k_mean_gather and k_mean_apply written out.  Only what compiles to the same text either way is
+// a function of the headers; the rest, put into one, reschedules the kernel around it
+// (profiles/tcfamily/README.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -47,23 +52,6 @@ using namespace g2048::nt;
 constexpr int RATE_BITS = G2048_STAGEDELAY_RATE_BITS;
 constexpr int MAXH = G2048_STAGEDELAY_MAX_HORIZON;
 static_assert(MAXH <= 8, "a board's group of 8 lanes holds one slot of the ring per lane");
-
-// The ring position of a board, clamped into the domain (head < H, depth <= H) so that a state
-// the caller corrupted cannot index past the planes.
-struct Ring {
-    uint32_t head, depth;
-};
-
-__device__ __forceinline__ Ring load_ring(const uint8_t* __restrict__ head,
-                                          const uint8_t* __restrict__ depth, int64_t i,
-                                          uint32_t H) {
-    return Ring{min((uint32_t)head[i], H - 1u), min((uint32_t)depth[i], H)};
-}
-
-// the plane k steps back from `head`, k < H
-__device__ __forceinline__ uint32_t plane_back(uint32_t head, uint32_t k, uint32_t H) {
-    return head >= k ? head - k : head + H - k;
-}
 
 template <int T>
 __global__ __launch_bounds__(POLICY_BLOCK) void k_delay_policy(
@@ -104,11 +92,8 @@ __global__ __launch_bounds__(POLICY_BLOCK) void k_delay_policy(
     for (int t = 0; t < T; ++t) psum += pv[t];
     psum = group_sum(psum);  // V(prev) in the group a == 0
     if (!l.live) return;
-    // promotion: the value the entry resolves to, into the entries this lane found UNSET.
-    // `unset` is 0 outside the groups a == 0 of boards with has_prev.
-#pragma unroll
-    for (int t = 0; t < T; ++t)
-        if ((unset >> t) & 1u) lut[pe[t]] = pv[t];
+    // `unset` is 0 outside the groups a == 0 of boards with has_prev
+    promote(lut, pe, pv, unset);
     // the group a == 0 holds V(prev) in every lane: lane k of it owns slot k of the ring
     const uint32_t k = l.lane & 31u;
     if (k >= H) return;
@@ -144,14 +129,11 @@ __global__ __launch_bounds__(UBLOCK) void k_delay_gather(
     int64_t* __restrict__ acc_, int64_t n, const uint4* __restrict__ hist,
     const uint8_t* __restrict__ head, const uint8_t* __restrict__ depth, uint32_t H,
     const int32_t* __restrict__ delta, Params p, StagedIndex ix) {
-    constexpr int SLOT_BITS = slot_bits<T>();
-    constexpr uint32_t SLOTS = 1u << SLOT_BITS;
-    static_assert(SLOTS * 16u <= 160u * 1024u, "the LDS table must fit a CU's 160 KiB");
-    __shared__ uint32_t keys[SLOTS];
-    __shared__ uint32_t csum[SLOTS];  // a block makes at most 1024 T H <= 2^16 hits
-    __shared__ u64 dsum[SLOTS];
-    clear_keys<SLOT_BITS, UBLOCK>(keys);
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
+    __shared__ uint32_t keys[gather_slots<T>()];
+    __shared__ uint32_t csum[gather_slots<T>()];  // a block makes at most 1024 T H <= 2^16 hits
+    __shared__ u64 dsum[gather_slots<T>()];
+    clear_keys<slot_bits<T>(), UBLOCK>(keys);
+    for (uint32_t s = threadIdx.x; s < gather_slots<T>(); s += UBLOCK) {
         csum[s] = 0u;
         dsum[s] = 0ull;
     }
@@ -171,22 +153,11 @@ __global__ __launch_bounds__(UBLOCK) void k_delay_gather(
         const uint64_t nib = nibbles(sym(hb, g));
         const u64 de = (u64)(int64_t)d;
 #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const uint32_t e = base + entry(p, nib, t);
-            const uint32_t slot = claim_slot<SLOT_BITS>(keys, e);
-            if (slot != NO_SLOT) {
-                atomicAdd(&dsum[slot], de);
-                atomicAdd(&csum[slot], 1u);
-            } else {
-                add_entry(acc, e, de, 1ull);
-            }
-        }
+        for (int t = 0; t < T; ++t)
+            gather_hit<T>(keys, csum, dsum, acc, base + entry(p, nib, t), de);
     }
     __syncthreads();
-    for (uint32_t s = threadIdx.x; s < SLOTS; s += UBLOCK) {
-        const uint32_t key = keys[s];
-        if (key != NO_KEY) add_entry(acc, key, dsum[s], (u64)csum[s]);
-    }
+    gather_flush<T>(keys, csum, dsum, acc);
 }
 
 template <int T>
@@ -253,22 +224,12 @@ extern "C" {
 const char* g2048_stagedelay_last_error(void) { return g_err.c_str(); }
 
 int32_t g2048_stagedelay_rate(int64_t E, int64_t A) {
-    if (A < 0 || A > G2048_STAGEDELAY_MAX_A)
-        return refuse(g_err, "stagedelay_rate: A = %lld outside [0, 2^62)", (long long)A);
-    if (E > A || E < -A)
-        return refuse(g_err, "stagedelay_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
-                      (long long)A);
-    return (int32_t)tc_rate<RATE_BITS>(E, A);
+    return checked_rate<RATE_BITS, G2048_STAGEDELAY_MAX_A>(g_err, "stagedelay_rate", E, A);
 }
 
 int64_t g2048_stagedelay_acc_bytes(const g2048_ntuple_spec* spec,
                                    const g2048_ntstage_spec* stages) {
-    const char* who = "stagedelay_acc_bytes";
-    int rc = check_spec(g_err, who, spec);
-    if (rc != G2048_OK) return rc;
-    rc = check_stages(g_err, who, stages);
-    if (rc != G2048_OK) return rc;
-    return table_bytes(*spec, stages->n_stages);
+    return staged_acc_bytes(g_err, "stagedelay_acc_bytes", spec, stages);
 }
 
 int g2048_stagedelay_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
@@ -279,15 +240,10 @@ int g2048_stagedelay_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spe
                           uint8_t* action_out_dev, int32_t* delta_out_dev, int64_t* err_out_dev,
                           int device_id, void* stream) {
     const char* who = "stagedelay_step";
-    int rc = check_staged(g_err, who, spec, stages, lut_dev, boards_dev, n);
+    int rc = check_staged_tc(g_err, who, spec, stages, lut_dev, boards_dev, n, acc_dev, ea_dev);
     if (rc != G2048_OK) return rc;
-    rc = check_acc(g_err, who, acc_dev);
+    rc = check_ptr(g_err, who, "g_dev", g_dev, 8);
     if (rc != G2048_OK) return rc;
-    rc = check_ea(g_err, who, ea_dev, acc_dev, table_bytes(*spec, stages->n_stages));
-    if (rc != G2048_OK) return rc;
-    if (g_dev == nullptr) return refuse(g_err, "%s: g_dev is NULL", who);
-    if (((uintptr_t)g_dev & 7u) != 0)
-        return refuse(g_err, "%s: g_dev must be 8-byte aligned", who);
     if (horizon < 1 || horizon > MAXH)
         return refuse(g_err, "%s: horizon = %d outside [1, %d]", who, horizon, MAXH);
     if (lam_shift < 1 || lam_shift > G2048_STAGEDELAY_MAX_LAM_SHIFT)
@@ -299,9 +255,8 @@ int g2048_stagedelay_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spe
     // the ring stands where prev / has_prev stand: hist for prev, head (and depth) for has_prev
     if (head_dev == nullptr || depth_dev == nullptr)
         return refuse(g_err, "%s: head_dev / depth_dev is NULL", who);
-    if (hist_dev == nullptr) return refuse(g_err, "%s: hist_dev is NULL", who);
-    if (((uintptr_t)hist_dev & 15u) != 0)
-        return refuse(g_err, "%s: hist_dev must be 16-byte aligned", who);
+    rc = check_ptr(g_err, who, "hist_dev", hist_dev, 16);
+    if (rc != G2048_OK) return rc;
     rc = check_td_args(g_err, who, hist_dev, head_dev, lr_num, lr_shift, action_out_dev,
                        delta_out_dev, err_out_dev);
     if (rc != G2048_OK) return rc;

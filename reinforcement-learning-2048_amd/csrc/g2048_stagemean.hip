@@ -38,12 +38,7 @@ const char* g2048_stagemean_last_error(void) { return g_err.c_str(); }
 
 int64_t g2048_stagemean_acc_bytes(const g2048_ntuple_spec* spec,
                                   const g2048_ntstage_spec* stages) {
-    const char* who = "stagemean_acc_bytes";
-    int rc = check_spec(g_err, who, spec);
-    if (rc != G2048_OK) return rc;
-    rc = check_stages(g_err, who, stages);
-    if (rc != G2048_OK) return rc;
-    return table_bytes(*spec, stages->n_stages);
+    return staged_acc_bytes(g_err, "stagemean_acc_bytes", spec, stages);
 }
 
 int g2048_stagemean_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,

@@ -12,7 +12,9 @@
 // m = floor(D / C) and, if m != 0, loads that entry's (E, A), adds (m * rate) >> RATE_BITS into
 // lut and stores (E + m, A + |m|).  ea is no argument of the policy launch: promotion copies the
 // weight only.  The step's three launches, why promotion needs no ordering and why ea needs no
-// atomics are argued in the headers.  Here are the entry points.
+// atomics are argued in the headers; g2048_stagedelay.hip and g2048_stageback.hip put the same
+// rule, the same checked rate and the same opening checks on their own schedules.  Here are the
+// entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,22 +42,12 @@ extern "C" {
 const char* g2048_stagemeantc_last_error(void) { return g_err.c_str(); }
 
 int32_t g2048_stagemeantc_rate(int64_t E, int64_t A) {
-    if (A < 0 || A > G2048_STAGEMEANTC_MAX_A)
-        return refuse(g_err, "stagemeantc_rate: A = %lld outside [0, 2^62)", (long long)A);
-    if (E > A || E < -A)
-        return refuse(g_err, "stagemeantc_rate: |E| = |%lld| exceeds A = %lld", (long long)E,
-                      (long long)A);
-    return (int32_t)tc_rate<RATE_BITS>(E, A);
+    return checked_rate<RATE_BITS, G2048_STAGEMEANTC_MAX_A>(g_err, "stagemeantc_rate", E, A);
 }
 
 int64_t g2048_stagemeantc_acc_bytes(const g2048_ntuple_spec* spec,
                                     const g2048_ntstage_spec* stages) {
-    const char* who = "stagemeantc_acc_bytes";
-    int rc = check_spec(g_err, who, spec);
-    if (rc != G2048_OK) return rc;
-    rc = check_stages(g_err, who, stages);
-    if (rc != G2048_OK) return rc;
-    return table_bytes(*spec, stages->n_stages);
+    return staged_acc_bytes(g_err, "stagemeantc_acc_bytes", spec, stages);
 }
 
 int g2048_stagemeantc_step(const g2048_ntuple_spec* spec, const g2048_ntstage_spec* stages,
@@ -65,11 +57,7 @@ int g2048_stagemeantc_step(const g2048_ntuple_spec* spec, const g2048_ntstage_sp
                            uint8_t* action_out_dev, int32_t* delta_out_dev, int64_t* err_out_dev,
                            int device_id, void* stream) {
     const char* who = "stagemeantc_step";
-    int rc = check_staged(g_err, who, spec, stages, lut_dev, boards_dev, n);
-    if (rc != G2048_OK) return rc;
-    rc = check_acc(g_err, who, acc_dev);
-    if (rc != G2048_OK) return rc;
-    rc = check_ea(g_err, who, ea_dev, acc_dev, table_bytes(*spec, stages->n_stages));
+    int rc = check_staged_tc(g_err, who, spec, stages, lut_dev, boards_dev, n, acc_dev, ea_dev);
     if (rc != G2048_OK) return rc;
     rc = check_td_args(g_err, who, prev_dev, has_prev_dev, lr_num, lr_shift, action_out_dev,
                        delta_out_dev, err_out_dev);

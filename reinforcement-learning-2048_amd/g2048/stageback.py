@@ -40,7 +40,7 @@ from . import _native as N
 from . import ntstage as NS
 from . import ntuple as NT
 from .ntmeantc import MeanTCState, default_meantc_lr_shift
-from .stagemeantc import StagedMeanTCState
+from .stagemeantc import StagedMeanTCState, StagedTCState, bound_rate_and_acc_bytes
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libg2048_stageback.so")
 MAX_HORIZON = 1 << 20     # include/g2048_stageback.h G2048_STAGEBACK_MAX_HORIZON
@@ -80,26 +80,7 @@ def check(rc: int, what: str = "g2048_stageback") -> None:
         raise N.NativeError(f"{what} failed ({rc}): {msg}")
 
 
-def rate(E: int, A: int) -> int:
-    """rate(E, A) of the header, in [0, 2^16] (host code of the library)."""
-    r = load().g2048_stageback_rate(int(E), int(A))
-    if r < 0:
-        raise ValueError(load().g2048_stageback_last_error().decode(errors="replace"))
-    return int(r)
-
-
-def acc_bytes(spec, bounds=()) -> int:
-    """Bytes of the (D, C) workspace of a spec with len(bounds) + 1 stages, and of `ea`: 16 per
-    staged entry each."""
-    bounds = tuple(int(b) for b in bounds)
-    if len(bounds) > NS.MAX_STAGES - 1 or any(not 1 <= b <= NS.MAX_BOUND for b in bounds):
-        raise ValueError(f"a staged network holds 1..{NS.MAX_STAGES} stages with bounds in "
-                         f"1..{NS.MAX_BOUND}")
-    r = load().g2048_stageback_acc_bytes(C.byref(NT._as_spec(spec)._c()),
-                                         C.byref(NS._c_stages(bounds)))
-    if r < 0:
-        raise ValueError(load().g2048_stageback_last_error().decode(errors="replace"))
-    return int(r)
+rate, acc_bytes = bound_rate_and_acc_bytes(load, "stageback")
 
 
 def _check_horizon(n_boards: int, horizon: int) -> None:
@@ -124,33 +105,30 @@ def traj_bytes(n_boards: int, horizon: int) -> int:
 _TRAJ = ("traj", "gain", "cur", "rec", "rep_n", "rep_k")
 
 
-class BackwardState:
+class BackwardState(StagedTCState):
     """The state of the rule for one StagedNTupleNetwork and `n_boards` boards, on the network's
-    device: the workspace `acc` and the accumulators `ea`, both int64 [S, T, 16^m, 2] as in
-    StagedMeanTCState, and per board two buffers of `horizon` afterstates, `traj` u8 [n, 2, L, 16]
-    with the gains `gain` i32 [n, 2, L], the buffer being recorded `cur` u8 [n] and the counters
-    `rec`, `rep_n`, `rep_k` [n] -- the header's u32, held in int32 tensors (torch has no arithmetic
-    on uint32; a count above 2^31 reads as negative) -- all zero when fresh.  On a GPU device it
-    steps through the library; on the CPU it only holds, saves and loads."""
+    device: the workspace `acc` and the accumulators `ea` of StagedTCState, and per board two
+    buffers of `horizon` afterstates, `traj` u8 [n, 2, L, 16] with the gains `gain` i32 [n, 2, L],
+    the buffer being recorded `cur` u8 [n] and the counters `rec`, `rep_n`, `rep_k` [n] -- the
+    header's u32, held in int32 tensors (torch has no arithmetic on uint32; a count above 2^31
+    reads as negative) -- all zero when fresh.  The trajectory holds episodes not yet learned, so
+    it is saved with `ea`.  On a GPU device it steps through the library; on the CPU it only
+    holds, saves and loads."""
+
+    _TENSORS = _TRAJ
+    rate = staticmethod(rate)
 
     def __init__(self, net: NS.StagedNTupleNetwork, n_boards: int, horizon: int = 4096):
-        if not isinstance(net, NS.StagedNTupleNetwork):
-            raise TypeError("net must be a StagedNTupleNetwork (a single table goes through "
-                            "StagedNTupleNetwork.from_network(net, ()))")
-        self.net = net
+        super().__init__(net)
         self.n, self.horizon = int(n_boards), int(horizon)
         _check_horizon(self.n, self.horizon)
         kw = dict(device=net.device)
-        self.acc = torch.zeros((*net.lut.shape, 2), dtype=torch.int64, **kw)
-        self.ea = torch.zeros((*net.lut.shape, 2), dtype=torch.int64, **kw)
         self.traj = torch.zeros((self.n, 2, self.horizon, 16), dtype=torch.uint8, **kw)
         self.gain = torch.zeros((self.n, 2, self.horizon), dtype=torch.int32, **kw)
         self.cur = torch.zeros(self.n, dtype=torch.uint8, **kw)
         self.rec = torch.zeros(self.n, dtype=torch.int32, **kw)
         self.rep_n = torch.zeros(self.n, dtype=torch.int32, **kw)
         self.rep_k = torch.zeros(self.n, dtype=torch.int32, **kw)
-
-    rate = staticmethod(rate)
 
     @classmethod
     def from_state(cls, state, net: NS.StagedNTupleNetwork, n_boards: int,
@@ -162,16 +140,7 @@ class BackwardState:
         if not isinstance(state, (StagedMeanTCState, MeanTCState)):
             raise TypeError("state must be a StagedMeanTCState or a g2048.ntmeantc.MeanTCState")
         st = cls(net, n_boards, horizon)
-        if state.net.spec.tuples != net.spec.tuples:
-            raise ValueError(f"the state's tuples {state.net.spec.tuples} are not this network's "
-                             f"{net.spec.tuples}")
-        if isinstance(state, StagedMeanTCState):
-            if state.net.bounds != net.bounds:
-                raise ValueError(f"the state's bounds {state.net.bounds} are not this network's "
-                                 f"{net.bounds}")
-            st.ea.copy_(state.ea)
-        else:
-            st.ea[0].copy_(state.ea)
+        st._adopt(state)
         return st
 
     def reset(self) -> None:
@@ -213,36 +182,6 @@ class BackwardState:
                 N.ptr(x_out), N.ptr(replay_out), N.ptr(err_out), dev.index, N.stream_of(dev)),
                 "g2048_stageback_step")
         return actions_out, delta_out, err_out
-
-    # ------------------------------------------------------------------ persistence
-    def state_dict(self) -> dict:
-        """Plain tensors only, so torch.load(weights_only=True) reads the file back: `ea` under
-        StagedMeanTCState's keys, plus the trajectory, which holds episodes not yet learned --
-        with it (and the table and the env) a run resumes bit for bit.  `acc` holds nothing
-        between steps and is not saved."""
-        out = {"tuples": torch.tensor(self.net.spec.tuples, dtype=torch.int64),
-               "bounds": torch.tensor(self.net.bounds, dtype=torch.int64), "ea": self.ea}
-        out.update({name: getattr(self, name) for name in _TRAJ})
-        return out
-
-    def load_state_dict(self, state: dict) -> None:
-        tuples = tuple(tuple(int(c) for c in t) for t in state["tuples"].tolist())
-        if tuples != self.net.spec.tuples:
-            raise ValueError(f"the file's tuples {tuples} are not this network's "
-                             f"{self.net.spec.tuples}")
-        bounds = tuple(int(b) for b in state["bounds"].tolist())
-        if bounds != self.net.bounds:
-            raise ValueError(f"the file's bounds {bounds} are not this network's "
-                             f"{self.net.bounds}")
-        for name in ("ea", *_TRAJ):
-            own, t = getattr(self, name), state[name]
-            if t.dtype != own.dtype or t.shape != own.shape:
-                raise ValueError(f"{name} must be {own.dtype} {tuple(own.shape)}")
-        for name in ("ea", *_TRAJ):
-            getattr(self, name).copy_(state[name])
-
-    def save(self, path) -> None:
-        torch.save({k: v.cpu() for k, v in self.state_dict().items()}, path)
 
     @classmethod
     def load(cls, path, net: NS.StagedNTupleNetwork) -> "BackwardState":

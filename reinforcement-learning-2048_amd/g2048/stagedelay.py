@@ -38,7 +38,7 @@ from . import _native as N
 from . import ntstage as NS
 from . import ntuple as NT
 from .ntmeantc import MeanTCState, default_meantc_lr_shift
-from .stagemeantc import StagedMeanTCState
+from .stagemeantc import StagedMeanTCState, StagedTCState, bound_rate_and_acc_bytes
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libg2048_stagedelay.so")
 MAX_HORIZON = 8           # include/g2048_stagedelay.h G2048_STAGEDELAY_MAX_HORIZON
@@ -76,46 +76,26 @@ def check(rc: int, what: str = "g2048_stagedelay") -> None:
         raise N.NativeError(f"{what} failed ({rc}): {msg}")
 
 
-def rate(E: int, A: int) -> int:
-    """rate(E, A) of the header, in [0, 2^16] (host code of the library)."""
-    r = load().g2048_stagedelay_rate(int(E), int(A))
-    if r < 0:
-        raise ValueError(load().g2048_stagedelay_last_error().decode(errors="replace"))
-    return int(r)
-
-
-def acc_bytes(spec, bounds=()) -> int:
-    """Bytes of the (D, C) workspace of a spec with len(bounds) + 1 stages, and of `ea`: 16 per
-    staged entry each."""
-    bounds = tuple(int(b) for b in bounds)
-    if len(bounds) > NS.MAX_STAGES - 1 or any(not 1 <= b <= NS.MAX_BOUND for b in bounds):
-        raise ValueError(f"a staged network holds 1..{NS.MAX_STAGES} stages with bounds in "
-                         f"1..{NS.MAX_BOUND}")
-    r = load().g2048_stagedelay_acc_bytes(C.byref(NT._as_spec(spec)._c()),
-                                          C.byref(NS._c_stages(bounds)))
-    if r < 0:
-        raise ValueError(load().g2048_stagedelay_last_error().decode(errors="replace"))
-    return int(r)
-
+rate, acc_bytes = bound_rate_and_acc_bytes(load, "stagedelay")
 
 _RING = ("hist", "head", "depth", "g")
 
 
-class DelayedLambdaState:
+class DelayedLambdaState(StagedTCState):
     """The state of the rule for one StagedNTupleNetwork and `n_boards` boards, on the network's
-    device: the workspace `acc` and the accumulators `ea`, both int64 [S, T, 16^m, 2] as in
-    StagedMeanTCState, and the ring of each board's last `horizon` afterstates: `hist` u8
-    [H, n, 16], `head` u8 [n] (the plane of the latest one), `depth` u8 [n] (how many the running
-    episode has) and `g` int64 [H, n] (the error sum each has collected), all zero when fresh.
-    lambda = 2^-lam_shift.  On a GPU device it steps through the library; on the CPU it only
-    holds, saves and loads."""
+    device: the workspace `acc` and the accumulators `ea` of StagedTCState, and the ring of each
+    board's last `horizon` afterstates: `hist` u8 [H, n, 16], `head` u8 [n] (the plane of the
+    latest one), `depth` u8 [n] (how many the running episode has) and `g` int64 [H, n] (the error
+    sum each has collected), all zero when fresh.  lambda = 2^-lam_shift.  The ring holds errors
+    not yet applied, so it is saved with `ea`, and a file's lam_shift must be the state's.  On a
+    GPU device it steps through the library; on the CPU it only holds, saves and loads."""
+
+    _TENSORS, _SCALARS = _RING, ("lam_shift",)
+    rate = staticmethod(rate)
 
     def __init__(self, net: NS.StagedNTupleNetwork, n_boards: int, horizon: int = 3,
                  lam_shift: int = 1):
-        if not isinstance(net, NS.StagedNTupleNetwork):
-            raise TypeError("net must be a StagedNTupleNetwork (a single table goes through "
-                            "StagedNTupleNetwork.from_network(net, ()))")
-        self.net = net
+        super().__init__(net)
         self.n, self.horizon, self.lam_shift = int(n_boards), int(horizon), int(lam_shift)
         if not 1 <= self.n <= N.MAX_BOARDS:
             raise ValueError(f"n_boards must be in [1, {N.MAX_BOARDS}]")
@@ -126,14 +106,10 @@ class DelayedLambdaState:
         if (self.horizon - 1) * self.lam_shift > MAX_LAM_SHIFT:
             raise ValueError(f"(horizon - 1) * lam_shift must not exceed {MAX_LAM_SHIFT}")
         kw = dict(device=net.device)
-        self.acc = torch.zeros((*net.lut.shape, 2), dtype=torch.int64, **kw)
-        self.ea = torch.zeros((*net.lut.shape, 2), dtype=torch.int64, **kw)
         self.hist = torch.zeros((self.horizon, self.n, 16), dtype=torch.uint8, **kw)
         self.head = torch.zeros(self.n, dtype=torch.uint8, **kw)
         self.depth = torch.zeros(self.n, dtype=torch.uint8, **kw)
         self.g = torch.zeros((self.horizon, self.n), dtype=torch.int64, **kw)
-
-    rate = staticmethod(rate)
 
     @classmethod
     def from_state(cls, state, net: NS.StagedNTupleNetwork, n_boards: int, horizon: int = 3,
@@ -145,16 +121,7 @@ class DelayedLambdaState:
         if not isinstance(state, (StagedMeanTCState, MeanTCState)):
             raise TypeError("state must be a StagedMeanTCState or a g2048.ntmeantc.MeanTCState")
         st = cls(net, n_boards, horizon, lam_shift)
-        if state.net.spec.tuples != net.spec.tuples:
-            raise ValueError(f"the state's tuples {state.net.spec.tuples} are not this network's "
-                             f"{net.spec.tuples}")
-        if isinstance(state, StagedMeanTCState):
-            if state.net.bounds != net.bounds:
-                raise ValueError(f"the state's bounds {state.net.bounds} are not this network's "
-                                 f"{net.bounds}")
-            st.ea.copy_(state.ea)
-        else:
-            st.ea[0].copy_(state.ea)
+        st._adopt(state)
         return st
 
     def reset(self) -> None:
@@ -190,40 +157,6 @@ class DelayedLambdaState:
                 int(lr_shift), N.ptr(actions_out), N.ptr(delta_out), N.ptr(err_out), dev.index,
                 N.stream_of(dev)), "g2048_stagedelay_step")
         return actions_out, delta_out, err_out
-
-    # ------------------------------------------------------------------ persistence
-    def state_dict(self) -> dict:
-        """Plain tensors only, so torch.load(weights_only=True) reads the file back: `ea` under
-        StagedMeanTCState's keys, plus the ring, which holds errors not yet applied -- with it
-        (and the table and the env) a run resumes bit for bit.  `acc` holds nothing between steps
-        and is not saved."""
-        out = {"tuples": torch.tensor(self.net.spec.tuples, dtype=torch.int64),
-               "bounds": torch.tensor(self.net.bounds, dtype=torch.int64), "ea": self.ea,
-               "lam_shift": torch.tensor(self.lam_shift, dtype=torch.int64)}
-        out.update({name: getattr(self, name) for name in _RING})
-        return out
-
-    def load_state_dict(self, state: dict) -> None:
-        tuples = tuple(tuple(int(c) for c in t) for t in state["tuples"].tolist())
-        if tuples != self.net.spec.tuples:
-            raise ValueError(f"the file's tuples {tuples} are not this network's "
-                             f"{self.net.spec.tuples}")
-        bounds = tuple(int(b) for b in state["bounds"].tolist())
-        if bounds != self.net.bounds:
-            raise ValueError(f"the file's bounds {bounds} are not this network's "
-                             f"{self.net.bounds}")
-        if int(state["lam_shift"]) != self.lam_shift:
-            raise ValueError(f"the file's lam_shift {int(state['lam_shift'])} is not this "
-                             f"state's {self.lam_shift}")
-        for name in ("ea", *_RING):
-            own, t = getattr(self, name), state[name]
-            if t.dtype != own.dtype or t.shape != own.shape:
-                raise ValueError(f"{name} must be {own.dtype} {tuple(own.shape)}")
-        for name in ("ea", *_RING):
-            getattr(self, name).copy_(state[name])
-
-    def save(self, path) -> None:
-        torch.save({k: v.cpu() for k, v in self.state_dict().items()}, path)
 
     @classmethod
     def load(cls, path, net: NS.StagedNTupleNetwork) -> "DelayedLambdaState":

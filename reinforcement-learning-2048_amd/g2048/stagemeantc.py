@@ -12,6 +12,9 @@ learners the rule is defined in integer arithmetic (see the header), its result 
 any order, a whole run is reproducible bit for bit and is checked bit for bit against
 tests/stagemeantc_ref.py.
 
+  StagedTCState(net)      the base of this state and of g2048.stagedelay's and g2048.stageback's,
+                          the same rule on other schedules: `acc`, `ea`, the adoption of another
+                          state's `ea`, state_dict() / load_state_dict() / save()
   StagedMeanTCState(net)  owns `acc`, int64 [S, T, 16^m, 2] ((D, C) per staged entry; a workspace
                           that is all zero between steps) and `ea`, int64 [S, T, 16^m, 2] (E and A
                           interleaved; it carries across steps): meantc_step(), rate(), save() /
@@ -70,44 +73,118 @@ def check(rc: int, what: str = "g2048_stagemeantc") -> None:
         raise N.NativeError(f"{what} failed ({rc}): {msg}")
 
 
-def rate(E: int, A: int) -> int:
-    """rate(E, A) of the header, in [0, 2^16] (host code of the library)."""
-    r = load().g2048_stagemeantc_rate(int(E), int(A))
-    if r < 0:
-        raise ValueError(load().g2048_stagemeantc_last_error().decode(errors="replace"))
-    return int(r)
+def bound_rate_and_acc_bytes(load, name: str):
+    """`rate` and `acc_bytes` of the staged mean-TC library that `load()` binds and whose symbols
+    start with g2048_`name`_: the three libraries of the rule export the same two host calls."""
+    def call(symbol, *args):
+        r = getattr(load(), f"g2048_{name}_{symbol}")(*args)
+        if r < 0:
+            raise ValueError(getattr(load(), f"g2048_{name}_last_error")().decode(
+                errors="replace"))
+        return int(r)
+
+    def rate(E: int, A: int) -> int:
+        """rate(E, A) of the header, in [0, 2^16] (host code of the library)."""
+        return call("rate", int(E), int(A))
+
+    def acc_bytes(spec, bounds=()) -> int:
+        """Bytes of the (D, C) workspace of a spec with len(bounds) + 1 stages, and of `ea`: 16
+        per staged entry each."""
+        bounds = tuple(int(b) for b in bounds)
+        if len(bounds) > NS.MAX_STAGES - 1 or any(not 1 <= b <= NS.MAX_BOUND for b in bounds):
+            raise ValueError(f"a staged network holds 1..{NS.MAX_STAGES} stages with bounds in "
+                             f"1..{NS.MAX_BOUND}")
+        return call("acc_bytes", C.byref(NT._as_spec(spec)._c()), C.byref(NS._c_stages(bounds)))
+
+    return rate, acc_bytes
 
 
-def acc_bytes(spec, bounds=()) -> int:
-    """Bytes of the (D, C) workspace of a spec with len(bounds) + 1 stages, and of `ea`: 16 per
-    staged entry each."""
-    bounds = tuple(int(b) for b in bounds)
-    if len(bounds) > NS.MAX_STAGES - 1 or any(not 1 <= b <= NS.MAX_BOUND for b in bounds):
-        raise ValueError(f"a staged network holds 1..{NS.MAX_STAGES} stages with bounds in "
-                         f"1..{NS.MAX_BOUND}")
-    r = load().g2048_stagemeantc_acc_bytes(C.byref(NT._as_spec(spec)._c()),
-                                           C.byref(NS._c_stages(bounds)))
-    if r < 0:
-        raise ValueError(load().g2048_stagemeantc_last_error().decode(errors="replace"))
-    return int(r)
+rate, acc_bytes = bound_rate_and_acc_bytes(load, "stagemeantc")
 
 
-class StagedMeanTCState:
-    """The state of the rule for one StagedNTupleNetwork, on the network's device: the workspace
+class StagedTCState:
+    """What the states of the staged mean-TC rule share, whatever the schedule: the workspace
     `acc` int64 [S, T, 16^m, 2], zeroed here and left all zero by every step, and the accumulators
     `ea` int64 [S, T, 16^m, 2], ea[s, t, i, 0] = E and ea[s, t, i, 1] = A of net.lut[s, t, i],
-    zero-initialised.  On a GPU device it steps through the library; on the CPU it only holds,
-    saves and loads."""
+    zero-initialised, on the network's device; the adoption of another state's `ea`; state_dict(),
+    load_state_dict() and save().  A subclass names what it carries beside `ea`: its tensors in
+    `_TENSORS` and its int attributes, which a file must match, in `_SCALARS`."""
+
+    _TENSORS: tuple = ()
+    _SCALARS: tuple = ()
 
     def __init__(self, net: NS.StagedNTupleNetwork):
         if not isinstance(net, NS.StagedNTupleNetwork):
-            raise TypeError("net must be a StagedNTupleNetwork (a single table goes to "
-                            "g2048.ntmeantc.MeanTCState)")
+            raise TypeError("net must be a StagedNTupleNetwork (a single table goes through "
+                            "StagedNTupleNetwork.from_network(net, ()))")
         self.net = net
         self.acc = torch.zeros((*net.lut.shape, 2), dtype=torch.int64, device=net.device)
         self.ea = torch.zeros((*net.lut.shape, 2), dtype=torch.int64, device=net.device)
 
+    def _adopt(self, state) -> None:
+        """`ea` of a run under another rule, copied to this state's device: a StagedTCState's as
+        it is (its network must have this one's tuples and bounds), or a single table's
+        MeanTCState's in stage 0 with zeros above (its network must have this one's tuples)."""
+        net = self.net
+        if state.net.spec.tuples != net.spec.tuples:
+            raise ValueError(f"the state's tuples {state.net.spec.tuples} are not this network's "
+                             f"{net.spec.tuples}")
+        if isinstance(state, MeanTCState):
+            self.ea[0].copy_(state.ea)
+            return
+        if state.net.bounds != net.bounds:
+            raise ValueError(f"the state's bounds {state.net.bounds} are not this network's "
+                             f"{net.bounds}")
+        self.ea.copy_(state.ea)
+
+    # ------------------------------------------------------------------ persistence
+    def state_dict(self) -> dict:
+        """Plain tensors only, so torch.load(weights_only=True) reads the file back: `ea` under
+        the same keys in every subclass, then the subclass's own, with which (and the table and
+        the env) a run resumes bit for bit.  `acc` holds nothing between steps and is not
+        saved."""
+        out = {"tuples": torch.tensor(self.net.spec.tuples, dtype=torch.int64),
+               "bounds": torch.tensor(self.net.bounds, dtype=torch.int64), "ea": self.ea}
+        out.update({k: torch.tensor(getattr(self, k), dtype=torch.int64) for k in self._SCALARS})
+        out.update({name: getattr(self, name) for name in self._TENSORS})
+        return out
+
+    def load_state_dict(self, state: dict) -> None:
+        tuples = tuple(tuple(int(c) for c in t) for t in state["tuples"].tolist())
+        if tuples != self.net.spec.tuples:
+            raise ValueError(f"the file's tuples {tuples} are not this network's "
+                             f"{self.net.spec.tuples}")
+        bounds = tuple(int(b) for b in state["bounds"].tolist())
+        if bounds != self.net.bounds:
+            raise ValueError(f"the file's bounds {bounds} are not this network's "
+                             f"{self.net.bounds}")
+        for k in self._SCALARS:
+            if int(state[k]) != getattr(self, k):
+                raise ValueError(f"the file's {k} {int(state[k])} is not this state's "
+                                 f"{getattr(self, k)}")
+        for name in ("ea", *self._TENSORS):
+            own, t = getattr(self, name), state[name]
+            if t.dtype != own.dtype or t.shape != own.shape:
+                raise ValueError(f"{name} must be {own.dtype} {tuple(own.shape)}")
+        for name in ("ea", *self._TENSORS):
+            getattr(self, name).copy_(state[name])
+
+    def save(self, path) -> None:
+        torch.save({k: v.cpu() for k, v in self.state_dict().items()}, path)
+
+
+class StagedMeanTCState(StagedTCState):
+    """The state of the rule for one StagedNTupleNetwork: `acc` and `ea` of StagedTCState and
+    nothing else.  On a GPU device it steps through the library; on the CPU it only holds, saves
+    and loads."""
+
     rate = staticmethod(rate)
+
+    def __init__(self, net: NS.StagedNTupleNetwork):
+        if not isinstance(net, NS.StagedNTupleNetwork):  # this rule has a single-table library
+            raise TypeError("net must be a StagedNTupleNetwork (a single table goes to "
+                            "g2048.ntmeantc.MeanTCState)")
+        super().__init__(net)
 
     @classmethod
     def from_state(cls, state: MeanTCState, net: NS.StagedNTupleNetwork) -> "StagedMeanTCState":
@@ -117,10 +194,7 @@ class StagedMeanTCState:
         if not isinstance(state, MeanTCState):
             raise TypeError("state must be a g2048.ntmeantc.MeanTCState")
         st = cls(net)
-        if state.net.spec.tuples != net.spec.tuples:
-            raise ValueError(f"the state's tuples {state.net.spec.tuples} are not this network's "
-                             f"{net.spec.tuples}")
-        st.ea[0].copy_(state.ea)
+        st._adopt(state)
         return st
 
     def meantc_step(self, boards, prev, has_prev, lr_num, lr_shift, actions_out, delta_out,
@@ -140,30 +214,6 @@ class StagedMeanTCState:
                 int(lr_shift), N.ptr(actions_out), N.ptr(delta_out), N.ptr(err_out), dev.index,
                 N.stream_of(dev)), "g2048_stagemeantc_step")
         return actions_out, delta_out, err_out
-
-    # ------------------------------------------------------------------ persistence
-    def state_dict(self) -> dict:
-        """Plain tensors only, so torch.load(weights_only=True) reads the file back.  `acc` holds
-        nothing between steps and is not saved."""
-        return {"tuples": torch.tensor(self.net.spec.tuples, dtype=torch.int64),
-                "bounds": torch.tensor(self.net.bounds, dtype=torch.int64), "ea": self.ea}
-
-    def load_state_dict(self, state: dict) -> None:
-        tuples = tuple(tuple(int(c) for c in t) for t in state["tuples"].tolist())
-        if tuples != self.net.spec.tuples:
-            raise ValueError(f"the file's tuples {tuples} are not this network's "
-                             f"{self.net.spec.tuples}")
-        bounds = tuple(int(b) for b in state["bounds"].tolist())
-        if bounds != self.net.bounds:
-            raise ValueError(f"the file's bounds {bounds} are not this network's "
-                             f"{self.net.bounds}")
-        ea = state["ea"]
-        if ea.dtype != torch.int64 or ea.shape != self.ea.shape:
-            raise ValueError(f"ea must be int64 {tuple(self.ea.shape)}")
-        self.ea.copy_(ea)
-
-    def save(self, path) -> None:
-        torch.save({k: v.cpu() for k, v in self.state_dict().items()}, path)
 
     @classmethod
     def load(cls, path, net: NS.StagedNTupleNetwork) -> "StagedMeanTCState":
